@@ -16,15 +16,26 @@ Timing: warmup runs W batches and then on to the next epoch boundary, so the
 K timed batches always start an epoch: the epoch's sampling commit, its event
 index (keys, radix sort, segments) and the prefetch of the next epoch's sample
 stream are inside the timed region (for K < batches this over-weights the
-per-epoch work; `epoch` in each schedule's record is one whole epoch timed the
-same way).
+per-epoch work; with --full, `epoch` in each schedule's record is one whole
+epoch timed the same way).
 
 Schedules (include/kb2e_engine.h kb2e_schedule): `value` is the PARALLEL
 schedule (the data-parallel form: the reference's sample stream, snapshot
 energies, hinge decisions and directions; summed row deltas and one norm per
-batch; link-prediction parity in DESIGN.md), and the same line carries the
-ORDERED schedule (bit-faithful to the reference) measured on the same
-workload under "schedules".
+batch; link-prediction parity in DESIGN.md), and with --full the same line
+carries the ORDERED schedule (bit-faithful to the reference) measured on the
+same workload under "schedules".
+
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline needs and
+no more: the seed tables, W warmup batches, the K timed batches of --schedule,
+the outputs if --dump-outputs is given, the line.  `--full` adds the rest: the
+other schedule under "schedules", the whole-epoch and late-epoch timings, and
+the CPU baseline (the reference on one core).
+
+--dump-outputs DIR: what a caller of the timed path holds after the last timed
+batch -- the entity, relation and weight tables (kb2e_download_params) and the
+loss / active-sample sums of the timed batches -- as DIR/<name>.npy (float64;
+at most 64 MB in all: of a larger table a fixed, seeded sample of rows).
 
 N>1 (torchrun): each rank owns the triples whose head hashes to it
  and runs batches of the single-GPU size over its shard
@@ -239,7 +250,29 @@ def phase_bytes(model, n, s, a):
     return score_b, fold_b
 
 
-def measure(args, schedule, ds, train, rank, world, local, dist, steps, warmup, seed_tabs=None, late=0):
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: all files together stay below this
+DUMP_SEED = 20  # the row sample of a table too large to write whole
+
+
+def dump_outputs(out_dir, ent, rel, w, loss, active):
+    """The arrays the timed path leaves its caller, as out_dir/<name>.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    tabs = {"entity": ent, "relation": rel}
+    if w is not None:
+        tabs["weights"] = w.reshape(w.shape[0], -1)
+    stats = np.array([loss, float(active)])
+    budget = DUMP_BYTES - stats.nbytes
+    share = budget // len(tabs)
+    whole = sum(t.nbytes for t in tabs.values()) <= budget
+    rng = np.random.default_rng(DUMP_SEED)
+    for name, t in tabs.items():
+        if not whole and t.nbytes > share:  # the same rows in every run: seeded, sorted
+            t = t[np.sort(rng.choice(t.shape[0], share // (t.shape[1] * t.itemsize), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(t, dtype=np.float64))
+    np.save(os.path.join(out_dir, "loss_active.npy"), stats)
+
+
+def measure(args, schedule, ds, train, rank, world, local, dist, steps, warmup, seed_tabs=None, late=0, dump_dir=None):
     """Train `warmup` then time `steps` batches of one schedule; returns a dict."""
     from kb2e_amd.engine import Engine
 
@@ -311,6 +344,8 @@ def measure(args, schedule, ds, train, rank, world, local, dist, steps, warmup, 
     elapsed = timed(steps)
     merge_s, merges = run.merge_s, run.merges
     loss, active = eng.take_stats()
+    if dump_dir is not None:  # the tables as the last timed batch left them
+        dump_outputs(dump_dir, *eng.download_params(), loss, active)
     device_bytes = eng.device_bytes()
     # phase B span: TransE/TransH "fold_phase" (ordered: per-row folds; parallel:
     # the apply kernels), TransR "apply" (parallel) or the relation owners (ordered)
@@ -464,7 +499,12 @@ def main():
     ap.add_argument("--config", default="transr_fb15k", choices=sorted(CONFIGS))
     ap.add_argument("--precision", type=int, default=64, choices=[32, 64])
     ap.add_argument("--schedule", default="parallel", choices=["ordered", "parallel"],
-                    help="schedule of the headline value; the other one is reported beside it")
+                    help="schedule of the headline value; --full reports the other one beside it")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the other schedule, the whole-epoch and late-epoch timings and the CPU "
+                         "baseline (each can be switched off: --only, --no-epoch, --late-epoch 0, --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the tables and loss / active sums after the last timed batch as DIR/<name>.npy")
     ap.add_argument("--only", action="store_true", help="measure the --schedule only")
     ap.add_argument("--sub-batches", type=int, default=None,
                     help="PARALLEL TransR sub-batches (kb2e_config.sub_batches; default: the engine's)")
@@ -476,6 +516,9 @@ def main():
     ap.add_argument("--dim", type=int, default=None,
                     help="another embedding width on the config's data (A/B lines, e.g. the n > 128 wide path)")
     args = ap.parse_args()
+    if not args.full:  # the plain run: the headline's own measurement only
+        args.only = args.no_cpu_baseline = args.no_epoch = True
+        args.late_epoch = 0
     if args.dim is not None:  # (the config's model and data at another width; named in config.dim)
         m_, sh_, _, me_, di_, ra_ = CONFIGS[args.config]
         CONFIGS[args.config] = (m_, sh_, args.dim, me_, di_, ra_)
@@ -511,7 +554,8 @@ def main():
         # every rank draws the same seed (fixed glibc seed), no broadcast needed
         seed_tabs = transe_seed(ds, dim, seed_tmp.name, epochs=args.seed_epochs, device=local if world > 1 else 0)
     main_run = measure(args, args.schedule, ds, train, rank, world, local, dist, args.steps, args.warmup, seed_tabs,
-                       late=args.late_epoch if shape != "k5" else 0)
+                       late=args.late_epoch if shape != "k5" else 0,
+                       dump_dir=args.dump_outputs if rank == 0 else None)
     other = "ordered" if args.schedule == "parallel" else "parallel"
     other_run = None
     if not args.only:

@@ -5,7 +5,7 @@
 #
 #   bash tools/gpu.sh suite    <tag> [pytest args]          the -m gpu suite, one process
 #   bash tools/gpu.sh tests    <tag> <pytest selection...>  selected GPU tests
-#   bash tools/gpu.sh bench    <tag> [bench.py args]        one bench line (default: the driver's)
+#   bash tools/gpu.sh bench    <tag> [bench.py args]        one bench line (--full: both schedules, epochs, CPU baseline)
 #   bash tools/gpu.sh ab       <tag> <config> <VAR> <v1> [v2 ...]   100-batch lines per env setting ("-" = unset)
 #   bash tools/gpu.sh profile  <tag> <schedule> [bench args]  bench + rocprofv3 trace + HBM / f64-MFMA PMC passes
 #   bash tools/gpu.sh envelope <tag> <model> <dim> <compat> <epochs> <seeds> [batches] [schedules] [sub-batches]
@@ -51,7 +51,7 @@ case "$CMD" in
     CFG=$1; VAR=$2; shift 2
     for V in "$@"; do
       if [ "$V" = "-" ]; then unset "$VAR"; else export "$VAR=$V"; fi
-      if [ -n "$AB_EPOCH" ]; then EP="--late-epoch 50"; else EP="--no-epoch"; fi
+      if [ -n "$AB_EPOCH" ]; then EP="--full --late-epoch 50"; else EP="--no-epoch"; fi
       bench_run "ab_${V}" 400 --config "$CFG" --only --no-cpu-baseline $EP --steps 100 --warmup 100 || exit 1
     done ;;
   k5stats)  # the chain kernels' phase counters (KB2E_RPAR_STATS) on the K5 line, per KB2E_RPAR_CHAIN value
@@ -76,7 +76,7 @@ PY
     tail -5 "$OUT/timeline.txt" ;;
   profile)
     SCHED=$1; shift
-    bench_run bench 400 --schedule "$SCHED" "$@" || exit 1
+    bench_run bench 400 --full --schedule "$SCHED" "$@" || exit 1
     PASS="--schedule $SCHED --only --no-cpu-baseline --no-epoch --steps 100 --warmup 100"
     timeout -k 10 400 rocprofv3 --kernel-trace --stats -T -d "$OUT/trace" -o run --output-format csv -- \
         python3 bench.py $PASS "$@" > "$OUT/trace.log" 2>&1 || fail trace $? "$OUT/trace.log"
@@ -117,7 +117,7 @@ PY
     bench_run k5 400 $K5 ;;
   final)
     pytest_run "$OUT/pytest.log" 1000 tests -m gpu || exit 1
-    bench_run default 600 || exit 1
+    bench_run default 600 --full || exit 1
     bench_run k5 400 $K5 ;;
   *) echo "unknown command $CMD"; exit 2 ;;
 esac
