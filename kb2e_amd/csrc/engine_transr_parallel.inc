@@ -134,7 +134,6 @@ void setup_transr_parallel(kb2e_ctx* c) {
         HIPCHK(hipHostMalloc((void**)h, (size_t)c->nbi * 4, 0));
         std::memset(*h, 0, (size_t)c->nbi * 4);
     }
-    // three pair-dedupe tables in rotation (sub-batches: phase A runs one sub-batch ahead)
     if (c->rpar_widep) c->rpar_wsc.alloc((size_t)c->rpar_brel_cap * c->n * c->ld * 8);
     else c->rpar_wsc.free();
     if (c->sub > 1) {  // the start-of-batch tables phase A reads while phase B runs sub-batch by sub-batch
@@ -155,7 +154,8 @@ void setup_transr_parallel(kb2e_ctx* c) {
     if (g.num_entities >= (1 << kPtabEntBits) - 1 || g.num_relations >= (1 << kPtabRelBits) - 1 ||
         c->B * 4 >= (1 << kPtabSlotBits))
         throw std::invalid_argument("PARALLEL TransR: at most 2^24 - 2 entities, 2^18 - 2 relations, 2^20 - 1 samples a batch");
-    {  // the pair-dedupe tables: >= 3x the batch's update slots, a power of two, all empty
+    {  // the pair-dedupe tables: >= 3x the batch's update slots, a power of two, all empty;
+       // three of them in rotation (sub-batches: phase A runs one sub-batch ahead)
         size_t sz = 1024;
         while (sz < (size_t)c->B * 4 * 3) sz <<= 1;
         c->rpar_ptab_mask = (uint32_t)(sz - 1);

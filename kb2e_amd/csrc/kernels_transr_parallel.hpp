@@ -124,9 +124,10 @@ static __attribute__((unused)) __global__ __launch_bounds__(1024) void rel_list_
 // (h', r), (t', r) or (entity[r], r) is the reference's repeated transRNorm
 // call on an already constrained row when an earlier active slot of the batch
 // holds the same (relation, entity) (transr/trainer.cpp:183-188), whichever tile
-// it falls in.  One word per entry, all ones = empty; two tables alternate by
-// batch, the inserting kernel of batch b clearing batch b + 1's (whose last
-// reader was batch b - 1's transRNorm step).
+// it falls in.  One word per entry, all ones = empty; three tables rotate by
+// sub-batch (phase A runs one sub-batch ahead of phase B): the inserting kernel of
+// sub-batch b fills table b % 3 and clears table (b + 1) % 3, whose last reader was
+// sub-batch b - 2's transRNorm step, while sub-batch b - 1's may still read its own.
 constexpr int kPtabEntBits = 24, kPtabRelBits = 18, kPtabSlotBits = 22;
 constexpr unsigned long long kPtabEmpty = ~0ull;
 

@@ -19,12 +19,24 @@
 // W_c -= lr A_k^T G_k is made by waves 1-3 at the start of chunk k+1, while wave
 // 0 walks chunk k+1, instead of between the two walks (a wave touches only its
 // own slices' columns of the P buffers, so reading G_k and writing X_{k+2} into
-// the same buffer need no barrier); the walker writes each violator's pair record
-// G to global memory as it publishes it, off the helpers' per-chunk work.  The walk keeps the chunk's projection
+// the same buffer need no barrier).  The walk keeps the chunk's projection
 // rows in registers (lane j: half l >> 5 of row j & 31), so a violator's
 // rank-1 move of the later rows is FMAs on registers with the violator's G row
-// read as LDS broadcasts.  The relation's last-update chunk starts after W_c's
-// rows are renormalised: its projections are then made afresh (all waves).
+// read as LDS broadcasts.  That update also writes the moved rows back, so the
+// chunk's rows in LDS stay current and a violator's row is read for V = p_v K0 as
+// it stands (broadcast reads, no row move between the pick and V), in small groups
+// with a group's FMAs under the next group's reads: the staging registers stay few
+// and K0's column never leaves the arch VGPRs.  (Taking p_v by v_readlane from the
+// two lanes that hold the row instead was measured and lost: 104 readlanes cost
+// 1.1k cycles a violator against 0.33k for the LDS form.)
+// The walker's only stores are to LDS: the rows, the violator's G row, its vl entry
+// and the publish word.  Everything of a chunk that goes to global memory -- the
+// violators' pair records G, their vio slots, the chunk's pair flags -- is written
+// by the helper waves from the published G rows (chunk_outputs), so the walker's
+// release store waits on no global store.  The relation's last-update chunk starts
+// after W_c's rows are renormalised: its projections are then made afresh (all
+// waves).  The KB2E_RPAR_STATS counters are a template parameter: the product
+// instantiation has no stamp code.
 #pragma once
 
 #include "kernels_transr_cons.hpp"  // pair_sum32
@@ -46,7 +58,9 @@ __host__ __device__ constexpr size_t pipe_lds(int n) {
            sizeof(int) * (size_t)(2 * kPipeList + kSeqMaxTiles + 1 + 8 + 2 * kChainRows);
 }
 
-template <typename T, int KS>
+// STATS: the KB2E_RPAR_STATS instantiation (cycle stamps of the phases, violator and
+// round counts); the product kernel carries none of it
+template <typename T, int KS, bool STATS>
 __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArgs a, RParBufs<T> bf) {
     using M = Mfma16<T>;
     static_assert(sizeof(T) == 8, "the D-row / k-step identity below is the FP64 fragment layout");
@@ -78,18 +92,21 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     int* pre = ps + kPipeList;
     int* misc = pre + kSeqMaxTiles + 1;
     int* vlist = misc + 8;  // [2][R] the chunks' violators in order, by chunk parity (misc[2]: the count)
-    const long long ck0 = clock64();
-    unsigned long long n_chunks = 0, n_vio = 0, n_rounds = 0, max_m = 0;
-    __shared__ unsigned long long ph[16];  // (LDS, not sixteen 64-bit registers)
-    if (threadIdx.x < 16) ph[threadIdx.x] = 0;
+    const long long ck0 = STATS ? clock64() : 0;
+    int n_chunks = 0;
+    unsigned long long n_vio = 0, n_rounds = 0, max_m = 0;
+    __shared__ unsigned long long ph[STATS ? 16 : 1];  // (LDS, not sixteen 64-bit registers)
+    if (STATS && threadIdx.x < 16) ph[threadIdx.x] = 0;
     long long tq = ck0;
     // (phases 12..15 on thread 64, helper wave 1: debt, tiles, helper_sync wait, rows +
     // corrections incl. the wait for the walk's end)
     auto tick = [&](int k) {
-        if (bf.stats && threadIdx.x == (k >= 12 || k == 5 ? 64u : 0u)) {
-            const long long t = clock64();
-            ph[k] += (unsigned long long)(t - tq);
-            tq = t;
+        if constexpr (STATS) {
+            if (threadIdx.x == (k >= 12 || k == 5 ? 64u : 0u)) {
+                const long long t = clock64();
+                ph[k] += (unsigned long long)(t - tq);
+                tq = t;
+            }
         }
     };
 
@@ -274,7 +291,15 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     // |p_j|^2 partials (qpart[0], the other slices' partials zero).  Sixteen threads a
     // row (one DPP row), NP / 16 columns each, rows rs, rs + 12, rs + 24.  The same
     // FMAs per element in the same order as correct_q.
-    auto correct_inc = [&](T* Pn, int cn, const T* Pc, const T* An, const T* Ac, const int* vl, int ck) {
+    // The chunk's outputs to global memory are made here too, off the walker: each
+    // violator's pair record G (da = -lr W G with the final matrix: chain_records) and
+    // vio slot as it is published (the sixteen threads of row group 0 hold the G row),
+    // and after the walk the chunk's pair flags from the walker's mask (misc[1 + 2 vpar],
+    // written before misc[6]); (entity'[r], r) marks the relation.  cn = 0 (the
+    // window's last chunk): the outputs alone.  base: the chunk's first pair in the
+    // window lists, cc its pairs.
+    auto chunk_outputs = [&](T* Pn, int cn, const T* Pc, const T* An, const T* Ac, const int* vl, int ck, int base,
+                             int cc, int vpar) {
         constexpr int NE = NP / 16, NPS = (R + 11) / 12;
         const int rs = ht >> 4, cb = (ht & 15) * NE;
         T x[NPS][NE];
@@ -291,37 +316,56 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
             const int avail = (pw >> 6) == ck ? (pw & 63) : 0;
             for (; used < avail; ++used) {
                 const int v = vl[used];
+                const int slv = ps[base + v];  // the violator's record slot (-2: (entity'[r], r))
                 T gv[NE], av[NE], d[NPS];
 #pragma unroll
                 for (int u = 0; u < NE; ++u) {
                     gv[u] = Pc[v * L + cb + u];
                     av[u] = Ac[v * L + cb + u];
                 }
+                if (cn > 0) {
 #pragma unroll
-                for (int p = 0; p < NPS; ++p) {  // a_{k+1}[j] . a_v, this thread's columns
-                    const int j = rs + 12 * p;
-                    d[p] = T(0);
+                    for (int p = 0; p < NPS; ++p) {  // a_{k+1}[j] . a_v, this thread's columns
+                        const int j = rs + 12 * p;
+                        d[p] = T(0);
 #pragma unroll
-                    for (int u = 0; u < NE; ++u) d[p] = fma(j < R ? An[j * L + cb + u] : T(0), av[u], d[p]);
-                }
-                row16_sums<T, NPS>(d);
+                        for (int u = 0; u < NE; ++u) d[p] = fma(j < R ? An[j * L + cb + u] : T(0), av[u], d[p]);
+                    }
+                    row16_sums<T, NPS>(d);
 #pragma unroll
-                for (int p = 0; p < NPS; ++p) {
-                    const int j = rs + 12 * p;
-                    if (j < cn) {
-                        const T gl = -lr * d[p];
+                    for (int p = 0; p < NPS; ++p) {
+                        const int j = rs + 12 * p;
+                        if (j < cn) {
+                            const T gl = -lr * d[p];
 #pragma unroll
-                        for (int u = 0; u < NE; ++u) x[p][u] = fma(gl, gv[u], x[p][u]);
+                            for (int u = 0; u < NE; ++u) x[p][u] = fma(gl, gv[u], x[p][u]);
+                        }
                     }
                 }
+                if (rs == 0) {
+                    T* dst = slv >= 0 ? bf.pair + (int64_t)slv * ld : bf.relpair + (int64_t)r * ld;
+#pragma unroll
+                    for (int u = 0; u < NE; ++u)
+                        if (cb + u < n) dst[cb + u] = gv[u];
+                    if (ht == 0) vio[nvt + used] = slv;
+                }
             }
-            if (done) break;
+            if (done) {
+                if (ht < cc) {
+                    const int sl = ps[base + ht];
+                    const bool vio_l = ((uint32_t)misc[1 + 2 * vpar] >> ht) & 1;
+                    if (sl >= 0) bf.pflag[sl] = vio_l ? 1 : 0;
+                    else if (vio_l) bf.relpair_stamp[r] = bf.stamp;
+                }
+                break;
+            }
             if (sp > (1u << 22)) {
                 if (l == 0) __hip_atomic_store(bf.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;
             }
             __builtin_amdgcn_s_sleep(1);
         }
+        if (cn == 0) return;
         T sq[NPS];
 #pragma unroll
         for (int p = 0; p < NPS; ++p) {
@@ -419,7 +463,7 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                     for (int s = 0; s < KS; ++s) reg[si * KS + s] = fma(ac[s], gc[si], reg[si * KS + s]);
                 }
         }
-        // (the pair records G were written by the walker as it published each violator)
+        // (the pair records G were written in chunk_outputs as the walker published each violator)
     };
     // the relation's last update renormalises W_c's rows before its own pairs'
     // shrinks (transr/trainer.cpp:178-180): row sums of the slices in DPP rows, then
@@ -559,7 +603,7 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
             T* Gm = Gbuf + pc * R * LG;
             T* Gn = Gbuf + (pc ^ 1) * R * LG;
             int* vl = vlist + par * R;
-            const int ck = (int)n_chunks;  // the chunk's tag in the publish words (misc[6], misc[7])
+            const int ck = n_chunks;  // the chunk's tag in the publish words (misc[6], misc[7])
             ++n_chunks;
             tick(1);
             if (w == 0) {
@@ -573,7 +617,7 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                     for (int v = 1; v < NB; ++v) q += qpart[v * R + j];
                 }
                 uint32_t vmask = 0;
-                int npub = 0;  // violators published to the helper waves (correct_inc)
+                int npub = 0;  // violators published to the helper waves (chunk_outputs)
                 if (__ballot(j < cc && q > T(1)) != 0) {
                     const T aaj = Gm[j * LG + j];  // |a_j|^2 (the Gram diagonal), off the violators' path
                     const int c0 = (l >> 5) * NH;
@@ -591,19 +635,41 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                         const T pp = readlane_f(q, v);
                         const T aa = readlane_f(aaj, v);
                         const T cjv = Gm[j * LG + v];  // a_j . a_v for the later rows' update
-                        const int slv = ps[base + v];  // the violator's record slot (-2: (entity'[r], r))
-                        // the violator's current row to LDS for the column-lane layout
-                        if (j == v) {
-#pragma unroll
-                            for (int u = 0; u < NH; ++u) P[v * L + c0 + u] = x[u];
-                        }
                         tick(4);
-                        const T pv = c < NP ? P[v * L + c] : T(0);
+                        // V = p_v K0.  The chunk's rows in LDS are current (the later rows' update
+                        // below writes them back), so the violator's row is read as it stands: no
+                        // row move on the path.  The row is staged in NG groups of k-steps, two
+                        // groups in flight, a group's FMAs under the next one's reads, so the
+                        // staging registers beside K0's column stay few; the four chains and
+                        // their order as ever.
                         T vv4[4] = {T(0), T(0), T(0), T(0)};
+                        constexpr int NG = 6;
+                        T pr[4 * KS];
+                        auto v_load = [&](int g) {
 #pragma unroll
-                        for (int t = 0; t < KS; ++t)
+                            for (int t = g * KS / NG; t < (g + 1) * KS / NG; ++t)
 #pragma unroll
-                            for (int u = 0; u < 4; ++u) vv4[u] = fma(P[v * L + 4 * t + u], reg[4 * t + u], vv4[u]);
+                                for (int u = 0; u < 4; ++u) pr[4 * t + u] = P[v * L + 4 * t + u];
+                        };
+                        auto v_fma = [&](int g) {
+#pragma unroll
+                            for (int t = g * KS / NG; t < (g + 1) * KS / NG; ++t)
+#pragma unroll
+                                for (int u = 0; u < 4; ++u) vv4[u] = fma(pr[4 * t + u], reg[4 * t + u], vv4[u]);
+                        };
+                        v_load(0);
+                        v_load(1);
+                        const T pv = c < NP ? P[v * L + c] : T(0);
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int g = 0; g < NG; ++g) {
+                            v_fma(g);
+                            if (g + 2 < NG) {
+                                __builtin_amdgcn_sched_barrier(0);
+                                v_load(g + 2);
+                                __builtin_amdgcn_sched_barrier(0);
+                            }
+                        }
                         const T Vc = c < n ? (vv4[0] + vv4[1]) + (vv4[2] + vv4[3]) : T(0);
                         tick(7);
                         T s2[2] = {pv * Vc, Vc * Vc};
@@ -625,28 +691,35 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                         const T rho = T(1) - eps * kappa;
                         T S0, S1;
                         const int m = transr_rounds_violator4(pp, w2, eps, rho, S0, S1);
-                        n_rounds += (unsigned long long)m;
-                        max_m = max_m > (unsigned long long)m ? max_m : (unsigned long long)m;
+                        if constexpr (STATS) {
+                            n_rounds += (unsigned long long)m;
+                            max_m = max_m > (unsigned long long)m ? max_m : (unsigned long long)m;
+                        }
                         const T cpf = T(2) * (S0 + eps * S1 * kappa), cvf = T(2) * eps * S1;
                         const T g = c < n ? cpf * pv - cvf * (Vc + aa * pv) : T(0);
                         tick(9);
-                        if (c < NP) P[v * L + c] = g;  // the violator's row now holds G
-                        {  // its pair record G (da = -lr W G with the final matrix: chain_records)
-                            T* dst = slv >= 0 ? bf.pair + (int64_t)slv * ld : bf.relpair + (int64_t)r * ld;
-                            if (c < n) dst[c] = g;
-                            if (l == 0) vio[nvt + npub] = slv;
-                        }
+                        // the violator's row now holds G (its pair record in global memory and
+                        // its vio slot are the helper waves', chunk_outputs)
+                        if (c < NP) P[v * L + c] = g;
                         tick(10);
                         const bool upd = j > v && j < cc;
                         T qh = T(0);  // this lane's half of |p_j|^2
                         if (upd) {
                             const T gl = -lr * cjv;
                             T s4[4] = {T(0), T(0), T(0), T(0)};
+                            // (every read of the G row in flight before the first FMA)
+                            T gr[NH];
+#pragma unroll
+                            for (int u = 0; u < NH; ++u) gr[u] = P[v * L + c0 + u];
+                            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                             for (int u = 0; u < NH; ++u) {
-                                x[u] = fma(gl, P[v * L + c0 + u], x[u]);
+                                x[u] = fma(gl, gr[u], x[u]);
                                 s4[u & 3] = fma(x[u], x[u], s4[u & 3]);
                             }
+                            // the row back to LDS: the next violator's row is read from there
+#pragma unroll
+                            for (int u = 0; u < NH; ++u) P[j * L + c0 + u] = x[u];
                             qh = (s4[0] + s4[1]) + (s4[2] + s4[3]);
                         }
                         {
@@ -662,17 +735,11 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                         ++npub;
                         vmask |= 1u << v;
                         cursor = v + 1;
-                        ++n_vio;
+                        if constexpr (STATS) ++n_vio;
                         tick(11);
                     }
                 }
-                if (l < cc) {  // the chunk's pair flags; (entity'[r], r) marks the relation
-                    const int sl = ps[base + l];
-                    const bool vio_l = (vmask >> l) & 1;
-                    if (sl >= 0) bf.pflag[sl] = vio_l ? 1 : 0;
-                    else if (vio_l) bf.relpair_stamp[r] = bf.stamp;
-                }
-                if (l == 0) {
+                if (l == 0) {  // (the chunk's pair flags: the helper waves, from this mask)
                     misc[1 + 2 * par] = (int)vmask;
                     misc[2 + 2 * par] = npub;
                     __hip_atomic_store(&misc[6], ck, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -691,7 +758,7 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                         if (hw + 3 * si < NB)
                             for (int rt = 0; rt < nrt; ++rt) proj_tile(An, rt, si, Pn);
                     // the Gram tiles to the helpers with the fewest projection tiles (the
-                    // same greedy choice on every helper); no cross Gram: correct_inc takes
+                    // same greedy choice on every helper); no cross Gram: chunk_outputs takes
                     // the few violators' dots a_{k+1}[j] . a_v on the fly
                     const int ng = nrt == 2 ? 3 : 1;
                     int load[3];
@@ -717,8 +784,9 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                     const int n3 = nb2 < npairs ? chunk_end(nb2) : nb2;
                     load_rows(n3, n3 < npairs ? chunk_end(n3) : n3);
                 }
-                // chunk k's violators into P_{k+1} as the walker publishes them, then |p|^2
-                if (cn > 0) correct_inc(Pn, cn, P, An, A, vl, ck);
+                // chunk k's violators into P_{k+1} as the walker publishes them, then |p|^2;
+                // its records and pair flags to global memory
+                chunk_outputs(Pn, cn, P, An, A, vl, ck, base, cc, par);
                 tick(15);
             }
             __syncthreads();  // B1: the walk, the next chunk's corrected projections and |p|^2
@@ -768,21 +836,21 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     if (mine && col < n)
         for (int jj = 0; jj < n; ++jj) bf.W[((int64_t)r * n + jj) * ld + col] = Wc[jj * L + col];
     chain_records<T, NP, L>(a, bf, r, vio, nvt, Wc, Pbuf, 2 * R * L);
-    if (bf.stats) {
+    if constexpr (STATS) {
         if (threadIdx.x == 0) {
             const unsigned long long cyc = (unsigned long long)(clock64() - ck0);
             atomicAdd(&g_seq_stats[0], 1ull);
-            atomicAdd(&g_seq_stats[1], n_chunks);
+            atomicAdd(&g_seq_stats[1], (unsigned long long)n_chunks);
             atomicAdd(&g_seq_stats[2], n_vio);
             atomicAdd(&g_seq_stats[3], n_rounds);
             atomicAdd(&g_seq_stats[4], cyc);
             atomicMax(&g_seq_stats[5], cyc);
-            atomicMax(&g_seq_stats[6], n_chunks);
+            atomicMax(&g_seq_stats[6], (unsigned long long)n_chunks);
             atomicMax(&g_seq_stats[7], max_m);
             for (int k = 0; k < 16; ++k) atomicAdd(&g_seq_stats[8 + k], ph[k]);
-            if (n_chunks >= 20) {
+            if (n_chunks >= 12) {  // (the hottest relation of a default half-batch walks 15-18 chunks)
                 for (int k = 0; k < 16; ++k) atomicAdd(&g_seq_stats[24 + k], ph[k]);
-                atomicAdd(&g_seq_stats[40], n_chunks);
+                atomicAdd(&g_seq_stats[40], (unsigned long long)n_chunks);
                 atomicAdd(&g_seq_stats[41], 1ull);
                 atomicAdd(&g_seq_stats[42], n_vio);
             }

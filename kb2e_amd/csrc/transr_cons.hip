@@ -51,15 +51,18 @@ const void* cons_fn(int n) {
     return kernel_fn<T>(kCons, n);
 }
 
-template <int... KS>
+template <bool STATS, int... KS>
 const void* pipe_table(int ks, std::integer_sequence<int, KS...>) {
-    const void* tab[] = {(const void*)transr_cons_pipe_kernel<double, KS + 1>...};
+    const void* tab[] = {(const void*)transr_cons_pipe_kernel<double, KS + 1, STATS>...};
     return tab[ks - 1];
 }
 
-const void* pipe_fn(int n) {
+// stats: the instantiation with the KB2E_RPAR_STATS counters (RParBufs::stats); the
+// product kernel has none of their code
+const void* pipe_fn(int n, bool stats) {
     if (!cons_wave_supported(n)) throw std::runtime_error("transRNorm pipelined chain kernel: n > 64");
-    return pipe_table((n + 3) / 4, std::make_integer_sequence<int, 16>{});
+    const auto seq = std::make_integer_sequence<int, 16>{};
+    return stats ? pipe_table<true>((n + 3) / 4, seq) : pipe_table<false>((n + 3) / 4, seq);
 }
 
 const void* chainw_fn(int n) {
@@ -97,7 +100,8 @@ bool use_wpipe(int n) {
 
 size_t cons_seq_setup(int n) {
     const size_t lds = pipe_lds<double>(n);
-    HIPCHK(hipFuncSetAttribute(pipe_fn(n), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (const bool stats : {false, true})
+        HIPCHK(hipFuncSetAttribute(pipe_fn(n, stats), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     return lds;
 }
 
@@ -107,7 +111,7 @@ void cons_seq_launch(const RParArgs& a, const RParBufs<double>& bf, size_t lds, 
     void* args[] = {&aa, &bb};
     // one workgroup per relation of the batch, most frequent first (chain_first_tile);
     // the pair records are made at the end of each relation's chain (chain_records)
-    HIPCHK(hipLaunchKernel(pipe_fn(a.n), dim3(chain_grid(a)), dim3(kChainThreads), args, lds, stream));
+    HIPCHK(hipLaunchKernel(pipe_fn(a.n, bf.stats != 0), dim3(chain_grid(a)), dim3(kChainThreads), args, lds, stream));
 }
 
 bool cons_chainw_supported(int n) { return n >= 1 && n <= kWideMaxN; }
