@@ -109,10 +109,9 @@ const char* kb2e_last_error(const kb2e_ctx* ctx);
 /* Trainer::add for every training triple, in train-file order, plus the
  * per-relation head/tail co-occurrence means of Trainer::loadFiles
  * (common/trainer.cpp:26-32, 151-201).  Builds the negative-sample filter and
- * the Bernoulli table on the device.  Contexts take dim <= 512 (ORDERED
- * TransR above dim 137 keeps the relation owner's matrix in L2 instead of LDS);
- * PARALLEL TransR trains dim <= 128, checked at kb2e_create
- * (KB2E_EUNSUPPORTED above). */
+ * the Bernoulli table on the device.  Contexts take dim <= 512 for every
+ * model and schedule, checked at kb2e_create (KB2E_EUNSUPPORTED above); wide
+ * TransR keeps a relation's matrix in L2 instead of LDS. */
 kb2e_status kb2e_upload_triples(kb2e_ctx* ctx, const int32_t* heads, const int32_t* tails,
                                 const int32_t* relations, int64_t count);
 
@@ -226,12 +225,59 @@ kb2e_status kb2e_evaluate_transr_compat(kb2e_ctx* ctx, const int32_t* heads, con
                                         int64_t nfilter, double* work, double* out,
                                         void (*progress)(double fraction, void* user), void* user);
 
+/* ---- Using a trained model.  The three calls below read the current device
+ * tables and change nothing: not the tables, the training state, the RNG or
+ * the TransR work vectors.  They use kb2e_evaluate's stateless energies for
+ * every model, distance, precision and dim a context takes: FP64 arithmetic
+ * with each sum in the reference's serial order (TransH is L1; TransR from
+ * zeroed work vectors; FP32 tables are widened to FP64 first).  transr_compat
+ * is ignored: the accumulating energy depends on every call made before and
+ * has no meaning for a stand-alone query.  Every device buffer they allocate
+ * is freed before they return (kb2e_device_bytes is the same before and
+ * after), and they return after a stream synchronisation. */
+
+/* energy[i] = tripleEnergy(heads[i], tails[i], relations[i]), bit-identical to
+ * transe/transe.cpp, transh/transh.cpp:10-29 and transr/transr.cpp:13-37 (with
+ * zeroed vectors).  count >= 1; an id out of range is KB2E_EINVAL. */
+kb2e_status kb2e_score_triples(kb2e_ctx* ctx, const int32_t* heads, const int32_t* tails,
+                               const int32_t* relations, int64_t count, double* energy);
+
+/* Top-k link prediction.  Query q is (entities[q], relations[q], side[q]); side
+ * follows the sample stream's convention: 1 = the tail is unknown, candidates
+ * (e, x, r) for every entity x; 0 = the head is unknown, candidates (x, e, r).
+ * A candidate whose triple is among the nfilter filter triples is excluded
+ * (nfilter == 0 with NULL arrays: nothing is).  Nothing else is excluded:
+ * x == e is a candidate, as in the reference's corruption loop -- and the true
+ * answer of a test triple is excluded too if the caller lists that triple in
+ * the filter (pass train + valid to rank the truth, train + valid + test to
+ * see only new answers).
+ * Per query: the k remaining candidates of smallest energy in ascending
+ * (energy, entity id) order in ids[q*k + j], energy[q*k + j];
+ * found[q] = min(k, |E| - excluded); slots at and after found[q] hold -1 and
+ * +inf.  1 <= k <= 1024 (k may exceed |E|).  KB2E_EINVAL: k out of range, a
+ * side other than 0 / 1, nq < 1, an id out of range in a query or the filter.
+ * The candidate keys of at most 1 GiB worth of queries are held at a time, so
+ * nq is not bounded by device memory. */
+kb2e_status kb2e_predict(kb2e_ctx* ctx, const int32_t* entities, const int32_t* relations, const int32_t* side,
+                         int64_t nq, int32_t k, const int32_t* filter_heads, const int32_t* filter_tails,
+                         const int32_t* filter_relations, int64_t nfilter, int32_t* ids, double* energy,
+                         int32_t* found);
+
+/* kb2e_evaluate's ranks per test triple, in the caller's order:
+ * ranks[i*4 + 0..3] = head raw, head filtered, tail raw, tail filtered rank of
+ * test triple i (1 + the candidates ranked above the truth; ties are not).
+ * kb2e_evaluate's four numbers are their means and <= 10 fractions. */
+kb2e_status kb2e_rank_triples(kb2e_ctx* ctx, const int32_t* heads, const int32_t* tails, const int32_t* relations,
+                              int64_t ntest, const int32_t* filter_heads, const int32_t* filter_tails,
+                              const int32_t* filter_relations, int64_t nfilter, int64_t* ranks);
+
 /* Raw glibc stream access (the context's RNG, as std::rand() in the reference). */
 int32_t kb2e_rng_next(kb2e_ctx* ctx);
 
 /* Timing of the engine's device kernels on the engine's own HIP stream (HIP
  * events around each launch; off by default).  `name` is a kernel family
- * ("score", "fold", "apply", "relowner", "index", "sample", ...).  Returns total
+ * ("score", "fold", "apply", "relowner", "index", "sample", ...; kb2e_predict:
+ * "predict_score", "predict_mask", "predict_select").  Returns total
  * milliseconds and launch count since kb2e_profile_enable.  on = 0: off;
  * on = P >= 1: the batch kernels of every P-th batch are timed (event records
  * cost device time of their own; sampling keeps the rest of the run unperturbed),

@@ -28,6 +28,7 @@
 #include "glibc_rand.hpp"
 #include "hip_util.hpp"
 #include "eval.hpp"
+#include "predict.hpp"
 #include "host_data.hpp"
 #include "kernels_common.hpp"
 #include "kernels_index.hpp"
@@ -1880,6 +1881,56 @@ kb2e_status kb2e_evaluate_transr_compat(kb2e_ctx* c, const int32_t* th, const in
         c->timed("eval", [&] {
             evaluate_transr_compat(eval_tables(c), EvalQuery{th, tt, tr, ntest, fh, ft, fr, nfilter}, work, out,
                                    progress, user);
+        });
+        return KB2E_OK;
+    });
+}
+
+namespace {
+// the predict kernel families on the engine's timers (kb2e_profile_query)
+PredictHooks predict_hooks(kb2e_ctx* c) {
+    return PredictHooks{c, [](void* ud) { return ((kb2e_ctx*)ud)->begin_span(); },
+                        [](void* ud, const char* name, hipEvent_t a) { ((kb2e_ctx*)ud)->end_span(name, a); }};
+}
+}  // namespace
+
+kb2e_status kb2e_score_triples(kb2e_ctx* c, const int32_t* heads, const int32_t* tails, const int32_t* relations,
+                               int64_t count, double* energy) {
+    return guarded(c, [&] {
+        if (!heads || !tails || !relations || count < 1 || !energy) return fail(c, KB2E_EINVAL, "no triples to score");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        score_triples(eval_tables(c), heads, tails, relations, count, energy);
+        return KB2E_OK;
+    });
+}
+
+kb2e_status kb2e_predict(kb2e_ctx* c, const int32_t* entities, const int32_t* relations, const int32_t* side,
+                         int64_t nq, int32_t k, const int32_t* fh, const int32_t* ft, const int32_t* fr,
+                         int64_t nfilter, int32_t* ids, double* energy, int32_t* found) {
+    return guarded(c, [&] {
+        if (!entities || !relations || !side || nq < 1 || !ids || !energy || !found || nfilter < 0 ||
+            (nfilter > 0 && (!fh || !ft || !fr)))
+            return fail(c, KB2E_EINVAL, "no queries");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        predict_topk(eval_tables(c), PredictQuery{entities, relations, side, nq, k, fh, ft, fr, nfilter}, ids, energy,
+                     found, &hooks);
+        return KB2E_OK;
+    });
+}
+
+kb2e_status kb2e_rank_triples(kb2e_ctx* c, const int32_t* th, const int32_t* tt, const int32_t* tr, int64_t ntest,
+                              const int32_t* fh, const int32_t* ft, const int32_t* fr, int64_t nfilter,
+                              int64_t* ranks) {
+    return guarded(c, [&] {
+        if (!th || !tt || !tr || ntest < 1 || !ranks || nfilter < 0 || (nfilter > 0 && (!fh || !ft || !fr)))
+            return fail(c, KB2E_EINVAL, "empty test set");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        c->timed("eval", [&] {
+            rank_triples_fixed(eval_tables(c), EvalQuery{th, tt, tr, ntest, fh, ft, fr, nfilter}, ranks);
         });
         return KB2E_OK;
     });

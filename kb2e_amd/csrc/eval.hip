@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "eval.hpp"
+#include "eval_shared.hpp"
 #include "hip_util.hpp"
 #include "host_data.hpp"
 #include "kernels_common.hpp"
@@ -43,71 +44,10 @@
 namespace kb2e {
 namespace {
 
-constexpr int kQ = 16;                   // queries per rank tile
 constexpr int kMaxCacheEntities = 40000;  // common/evaluation.h:11
-constexpr size_t kLdsMax = 160 * 1024;
-
-// host_data.hpp mix64 on the device: the FilterSet slot of a key
-__device__ __forceinline__ uint64_t eval_mix64(uint64_t x) {
-    x ^= x >> 31;
-    x *= 0x7fb5d329728ea185ull;
-    x ^= x >> 27;
-    x *= 0x81dadef4bc2dd44dull;
-    x ^= x >> 33;
-    return x;
-}
-
-struct FilterView {
-    const uint64_t* slots;
-    uint64_t mask, nr64, ne64;
-    __device__ __forceinline__ bool has(int64_t h, int64_t r, int64_t t) const {
-        const uint64_t k = ((uint64_t)h * nr64 + (uint64_t)r) * ne64 + (uint64_t)t;
-        uint64_t p = eval_mix64(k) & mask;
-        while (true) {
-            const uint64_t s = slots[p];
-            if (s == k) return true;
-            if (s == ~0ull) return false;
-            p = (p + 1) & mask;
-        }
-    }
-};
 
 // ------------------------------------------------------------ fixed energies
-
-template <typename T>
-struct ProjArgs {
-    int32_t model, n, ld, ne, r;
-    const T* ent;
-    const T* rel;
-    const T* w;
-    double* PT;    // [n][ne]
-    double* relv;  // [n] relation r in FP64
-};
-
-// One thread per entity: its projection for relation r, in FP64, summed in the
-// reference's order.
-template <typename T>
-__global__ __launch_bounds__(256) void eval_project_kernel(ProjArgs<T> a) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    for (int k = i; k < a.n; k += (int)(gridDim.x * blockDim.x)) a.relv[k] = (double)a.rel[(int64_t)a.r * a.ld + k];
-    if (i >= a.ne) return;
-    const T* e = a.ent + (int64_t)i * a.ld;
-    if (a.model == 0) {
-        for (int k = 0; k < a.n; ++k) a.PT[(int64_t)k * a.ne + i] = (double)e[k];
-    } else if (a.model == 1) {
-        const T* w = a.w + (int64_t)a.r * a.ld;
-        double s = 0;
-        for (int k = 0; k < a.n; ++k) s += (double)w[k] * (double)e[k];
-        for (int k = 0; k < a.n; ++k) a.PT[(int64_t)k * a.ne + i] = (double)e[k] - s * (double)w[k];
-    } else {
-        const T* W = a.w + (int64_t)a.r * a.n * a.ld;
-        for (int k = 0; k < a.n; ++k) {
-            double s = 0;
-            for (int j = 0; j < a.n; ++j) s += (double)W[(int64_t)j * a.ld + k] * (double)e[j];
-            a.PT[(int64_t)k * a.ne + i] = s;
-        }
-    }
-}
+// (FilterView, eval_project_kernel, kQ: eval_shared.hpp)
 
 struct RankArgs {
     const double* PT;    // [n][ne]
@@ -494,24 +434,12 @@ void build_filter(const EvalTables& t, const EvalQuery& q, DeviceFilter& df) {
     HIPCHK(hipMemcpyAsync(df.slots.p, df.fs.slots.data(), df.fs.slots.size() * 8, hipMemcpyHostToDevice, t.stream));
 }
 
-template <typename K>
-void allow_lds(K kernel, size_t bytes) {
-    HIPCHK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-}
-
 void finish(long long rawSum, long long filtSum, long long rawHits, long long filtHits, int64_t ntest, double* out) {
     const double nc = (double)ntest * 2.0;  // common/evaluation.cpp:246-250
     out[0] = rawSum / nc;
     out[1] = rawHits / nc;
     out[2] = filtSum / nc;
     out[3] = filtHits / nc;
-}
-
-template <typename T>
-void project(const EvalTables& t, int r, double* PT, double* relv) {
-    ProjArgs<T> a{t.model, t.n, t.ld, t.ne, r, (const T*)t.ent, (const T*)t.rel, (const T*)t.w, PT, relv};
-    eval_project_kernel<T><<<(std::max(t.ne, t.n) + 255) / 256, 256, 0, t.stream>>>(a);
-    HIPCHK(hipGetLastError());
 }
 
 template <typename T, int CH>
@@ -538,9 +466,12 @@ void run_chain(const EvalTables& t, CompatChainArgs<T> a) {
     }
 }
 
-}  // namespace
-
-void evaluate_fixed(const EvalTables& t, const EvalQuery& q, double out[4]) {
+// The ranking both entry points share: counts[x * 4 + c] of the x-th test triple
+// in relation-grouped order (c: head raw, head filtered, tail raw, tail
+// filtered = candidates ranked above the truth), order[x] = its index in the
+// caller's arrays.
+void fixed_counts(const EvalTables& t, const EvalQuery& q, std::vector<unsigned long long>& counts,
+                  std::vector<int64_t>& order) {
     if (q.ntest < 1) throw std::invalid_argument("empty test set");
     const int ne = t.ne, n = t.n;
     // n <= 600; KB2E_EVAL_ROWS_L2=1 forces the L2 form (tests)
@@ -556,6 +487,7 @@ void evaluate_fixed(const EvalTables& t, const EvalQuery& q, double out[4]) {
         for (int64_t k : g.byrel[r]) {
             qh.push_back(q.th[k]);
             qt.push_back(q.tt[k]);
+            order.push_back(k);
         }
         qoff[r + 1] = (int64_t)qh.size();
     }
@@ -595,11 +527,19 @@ void evaluate_fixed(const EvalTables& t, const EvalQuery& q, double out[4]) {
         else eval_rank_kernel<false><<<grid, 256, 0, t.stream>>>(ra);
         HIPCHK(hipGetLastError());
     }
-    std::vector<unsigned long long> counts(qh.size() * 4);
+    counts.assign(qh.size() * 4, 0);
     HIPCHK(hipMemcpyAsync(counts.data(), d_counts.p, counts.size() * 8, hipMemcpyDeviceToHost, t.stream));
     HIPCHK(hipStreamSynchronize(t.stream));
+}
+
+}  // namespace
+
+void evaluate_fixed(const EvalTables& t, const EvalQuery& q, double out[4]) {
+    std::vector<unsigned long long> counts;
+    std::vector<int64_t> order;
+    fixed_counts(t, q, counts, order);
     long long rawSum = 0, filtSum = 0, rawHits = 0, filtHits = 0;
-    for (size_t x = 0; x < qh.size(); ++x) {
+    for (size_t x = 0; x < order.size(); ++x) {
         for (int side = 0; side < 2; ++side) {
             const long long raw = 1 + (long long)counts[x * 4 + 2 * side];
             const long long filt = 1 + (long long)counts[x * 4 + 2 * side + 1];
@@ -610,6 +550,14 @@ void evaluate_fixed(const EvalTables& t, const EvalQuery& q, double out[4]) {
         }
     }
     finish(rawSum, filtSum, rawHits, filtHits, q.ntest, out);
+}
+
+void rank_triples_fixed(const EvalTables& t, const EvalQuery& q, int64_t* ranks) {
+    std::vector<unsigned long long> counts;
+    std::vector<int64_t> order;
+    fixed_counts(t, q, counts, order);
+    for (size_t x = 0; x < order.size(); ++x)
+        for (int c = 0; c < 4; ++c) ranks[order[x] * 4 + c] = 1 + (int64_t)counts[x * 4 + c];
 }
 
 void evaluate_transr_compat(const EvalTables& t, const EvalQuery& q, double* work, double out[5],

@@ -31,6 +31,12 @@ struct EvalQuery {
 // out = raw mean rank, raw hits@10, filtered mean rank, filtered hits@10.
 void evaluate_fixed(const EvalTables& t, const EvalQuery& q, double out[4]);
 
+// The same ranking per test triple: ranks[i * 4 + 0..3] = head raw, head
+// filtered, tail raw, tail filtered rank (1 + candidates ranked above the
+// truth) of test triple i, in the caller's order.  evaluate_fixed's four
+// numbers are the means and <= 10 fractions of these.
+void rank_triples_fixed(const EvalTables& t, const EvalQuery& q, int64_t* ranks);
+
 // TransR with the reference's accumulating energy work vectors
 // (transr/transr.cpp:20-25, transr/evaluation.cpp:22-32) through its cached,
 // relation-major loop (common/evaluation.cpp:107-121, 181-238).  work[2n] =

@@ -1,5 +1,8 @@
 // kb2e_cli.cpp -- drop-in command-line front end: trainTransE / trainTransH /
-// trainTransR and evalTransE / evalTransH / evalTransR (dispatch on argv[0]).
+// trainTransR and evalTransE / evalTransH / evalTransR (dispatch on argv[0]),
+// plus predictTransE / predictTransH / predictTransR (no reference counterpart:
+// top-k answers to (h, ?, r) / (?, t, r) queries from the trained tables;
+// --queries FILE, --topk K, --filtered 0|1).
 //
 // Same flags, defaults, stdout lines and files as the reference binaries
 // (transe/bin/trainTransE.cpp, common/args.cpp, common/loader.cpp,
@@ -111,6 +114,9 @@ void printUsage(const char* invoked) {  // common/args.cpp:125-142
     printf("   --schedule [0] (GPU: 0 ordered = the reference's sequence, 1 parallel)\n");
     printf("   --gpus [1] (GPU: devices --device .. --device+N-1, triples sharded by head, epoch merge over RCCL)\n");
     printf("   --subbatches [engine default] (GPU, parallel TransR: each batch's updates in this many sub-batches)\n");
+    printf("   --queries FILE (predictTrans*: head<TAB>tail<TAB>relation lines, ? for the unknown head or tail)\n");
+    printf("   --topk [10] (predictTrans*)\n");
+    printf("   --filtered [1] (predictTrans*: known triples are not answers)\n");
 }
 
 EmbeddingArguments parseArgs(int argc, char** argv) {  // common/args.cpp:53-122
@@ -411,12 +417,16 @@ double vec_len(const double* a, int n) {
     return std::sqrt(res);
 }
 
-// EmbeddingEvaluation::prepare + run (common/evaluation.cpp:181-266) with the
-// ranking on the GPU (kb2e_evaluate; TransR with --transrcompat 1, the default:
-// kb2e_evaluate_transr_compat, the reference's stateful energy).
-int eval_main(int argc, char** argv, kb2e_model model) {
-    EmbeddingArguments args = parseArgs(argc, argv);
-    printf("%s\n", args.to_string().c_str());
+// What the eval and predict binaries load: the id files, the three triple files
+// (test triples; filter = test + train + valid, common/evaluation.cpp:41-62) and
+// a context holding the embedding files (EmbeddingEvaluation::loadEmbeddings).
+struct LoadedModel {
+    std::map<std::string, int> entity2id, relation2id;
+    std::vector<int> th, tt, tr, fh, ft, fr;
+    kb2e_ctx* ctx = nullptr;
+};
+
+void load_model(const EmbeddingArguments& args, kb2e_model model, LoadedModel& L) {
     const std::string m = method_name(args.method);
     const std::string relPath = args.outputDir + "/relation2vec." + m;
     const std::string entPath = args.outputDir + "/entity2vec." + m;
@@ -429,11 +439,12 @@ int eval_main(int argc, char** argv, kb2e_model model) {
         printf("Could not find entity embedding file: %s. Make sure to specify the path and/or train.\n", entPath.c_str());
         exit(2);
     }
-    std::map<std::string, int> entity2id, relation2id;
+    std::map<std::string, int>& entity2id = L.entity2id;
+    std::map<std::string, int>& relation2id = L.relation2id;
     loadIdFile(args.dataDir + "/entity2id.txt", entity2id);
     loadIdFile(args.dataDir + "/relation2id.txt", relation2id);
     const int ne = (int)entity2id.size(), nr = (int)relation2id.size(), n = args.embeddingSize;
-    std::vector<int> th, tt, tr, fh, ft, fr;
+    std::vector<int>&th = L.th, &tt = L.tt, &tr = L.tr, &fh = L.fh, &ft = L.ft, &fr = L.fr;
     auto addFilter = [&](int h, int t, int r) { fh.push_back(h); ft.push_back(t); fr.push_back(r); };
     loadTripleFile(args.dataDir + "/test.txt", entity2id, relation2id, [&](int h, int t, int r) {
         th.push_back(h); tt.push_back(t); tr.push_back(r); addFilter(h, t, r); });
@@ -453,7 +464,7 @@ int eval_main(int argc, char** argv, kb2e_model model) {
     cfg.distance = args.distanceType;
     cfg.precision = 64;
     cfg.device = args.device;
-    kb2e_ctx* ctx = nullptr;
+    kb2e_ctx*& ctx = L.ctx;
     check(nullptr, kb2e_create(&cfg, &ctx), "create");
     // the embedding files parsed on the device (EmbeddingEvaluation::loadEmbeddings)
     if (kb2e_read_table(ctx, 1, relPath.c_str(), KB2E_READ_VERBATIM) != KB2E_OK) {
@@ -476,6 +487,18 @@ int eval_main(int argc, char** argv, kb2e_model model) {
         printf("Failed to read embedding weight values from seed file: '%s'\n", wPath.c_str());
         exit(1);
     }
+}
+
+// EmbeddingEvaluation::prepare + run (common/evaluation.cpp:181-266) with the
+// ranking on the GPU (kb2e_evaluate; TransR with --transrcompat 1, the default:
+// kb2e_evaluate_transr_compat, the reference's stateful energy).
+int eval_main(int argc, char** argv, kb2e_model model) {
+    EmbeddingArguments args = parseArgs(argc, argv);
+    printf("%s\n", args.to_string().c_str());
+    LoadedModel L;
+    load_model(args, model, L);
+    kb2e_ctx* ctx = L.ctx;
+    std::vector<int>&th = L.th, &tt = L.tt, &tr = L.tr, &fh = L.fh, &ft = L.ft, &fr = L.fr;
     double out[5];
     if (model == KB2E_TRANSR && args.transrCompat) {
         // the reference's evalTransR: energy work vectors accumulate over the
@@ -499,6 +522,78 @@ int eval_main(int argc, char** argv, kb2e_model model) {
     return 0;
 }
 
+// predictTransE|H|R: the reference's flags and files as evalTrans* loads them,
+// plus --queries FILE (lines "head<TAB>tail<TAB>relation" in the triple files'
+// column order with a literal ? for the unknown head or tail), --topk K [10]
+// and --filtered 0|1 [1: known triples (train + valid + test) are not answers].
+// One line per answer: query index (its line in FILE, from 0), position
+// (from 1), entity name, energy.
+int predict_main(int argc, char** argv, kb2e_model model) {
+    EmbeddingArguments args = parseArgs(argc, argv);
+    printf("%s\n", args.to_string().c_str());
+    int i, topk = 10, filtered = 1;
+    std::string queries;
+    if ((i = argpos("queries", true, argc, argv)) != -1) queries = argv[i + 1];
+    if ((i = argpos("topk", true, argc, argv)) != -1) topk = atoi(argv[i + 1]);
+    if ((i = argpos("filtered", true, argc, argv)) != -1) filtered = atoi(argv[i + 1]);
+    if (queries.empty()) {
+        printf("Argument missing for queries\n");
+        exit(1);
+    }
+    FILE* f = fopen(queries.c_str(), "r");
+    if (!f) {
+        printf("Could not open query file: %s\n", queries.c_str());
+        exit(2);
+    }
+    LoadedModel L;
+    load_model(args, model, L);
+    std::vector<std::string> names(L.entity2id.size());
+    for (const auto& kv : L.entity2id)
+        if (kv.second >= 0 && (size_t)kv.second < names.size()) names[(size_t)kv.second] = kv.first;
+    std::vector<int32_t> qe, qr, qs, qline;
+    char hb[512], tb[512], rb[512];
+    for (int line = 0; fscanf(f, "%511s\t%511s\t%511s", hb, tb, rb) == 3; ++line) {
+        const bool noHead = !strcmp(hb, "?"), noTail = !strcmp(tb, "?");
+        bool fail = false;
+        if (noHead == noTail) {
+            std::cout << "Query needs exactly one ? in the head or the tail column: " << hb << ' ' << tb << std::endl;
+            fail = true;
+        }
+        if (!noHead && !L.entity2id.count(hb)) {
+            std::cout << "Head entity found in triple file that was not found in the identity file: " << hb << std::endl;
+            fail = true;
+        }
+        if (!noTail && !L.entity2id.count(tb)) {
+            std::cout << "Tail entity found in triple file that was not found in the identity file: " << tb << std::endl;
+            fail = true;
+        }
+        if (!L.relation2id.count(rb)) {
+            std::cout << "Relation found in triple file that was not found in the identity file: " << rb << std::endl;
+            fail = true;
+        }
+        if (fail) continue;
+        qe.push_back(L.entity2id[noTail ? hb : tb]);
+        qr.push_back(L.relation2id[rb]);
+        qs.push_back(noTail ? 1 : 0);
+        qline.push_back(line);
+    }
+    fclose(f);
+    if (!qe.empty()) {
+        const size_t nq = qe.size(), k = (size_t)std::max(topk, 1);
+        std::vector<int32_t> ids(nq * k), found(nq);
+        std::vector<double> energy(nq * k);
+        const int64_t nf = filtered ? (int64_t)L.fh.size() : 0;
+        check(L.ctx, kb2e_predict(L.ctx, qe.data(), qr.data(), qs.data(), (int64_t)nq, topk, nf ? L.fh.data() : nullptr,
+                                  nf ? L.ft.data() : nullptr, nf ? L.fr.data() : nullptr, nf, ids.data(),
+                                  energy.data(), found.data()), "predict");
+        for (size_t q = 0; q < nq; ++q)
+            for (int j = 0; j < found[q]; ++j)
+                printf("%d\t%d\t%s\t%.6lf\n", qline[q], j + 1, names[(size_t)ids[q * k + j]].c_str(), energy[q * k + j]);
+    }
+    kb2e_destroy(L.ctx);
+    return 0;
+}
+
 }  // namespace kb2e_host
 
 #ifndef KB2E_CLI_NO_MAIN  // (tests/native/host_check.cpp includes this file for its parser and loader)
@@ -513,7 +608,10 @@ int main(int argc, char** argv) {
     if (prog == "evalTransE") return eval_main(argc, argv, KB2E_TRANSE);
     if (prog == "evalTransH") return eval_main(argc, argv, KB2E_TRANSH);
     if (prog == "evalTransR") return eval_main(argc, argv, KB2E_TRANSR);
-    fprintf(stderr, "invoke as trainTransE|H|R or evalTransE|H|R (got %s)\n", prog.c_str());
+    if (prog == "predictTransE") return predict_main(argc, argv, KB2E_TRANSE);
+    if (prog == "predictTransH") return predict_main(argc, argv, KB2E_TRANSH);
+    if (prog == "predictTransR") return predict_main(argc, argv, KB2E_TRANSR);
+    fprintf(stderr, "invoke as trainTransE|H|R, evalTransE|H|R or predictTransE|H|R (got %s)\n", prog.c_str());
     return 2;
 }
 #endif

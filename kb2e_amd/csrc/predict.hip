@@ -1,0 +1,588 @@
+// predict.hip -- top-k link-prediction queries and triple scoring on the device.
+// Part of libkb2e.so (kb2e_predict, kb2e_score_triples in engine.hip call in here).
+//
+// A query (e, r, side) asks for the k entities x of smallest energy of
+// (e, x, r) (side 1: the tail is unknown) or (x, e, r) (side 0: the head is),
+// known triples excluded.  Energies are the evaluator's stateless ones:
+// eval_project_kernel projects every entity for one relation, and
+// predict_score_kernel -- the one-sided form of eval_rank_kernel, same operand
+// order, so the same bits -- gives one thread per candidate and a tile of kQ
+// queries, and stores each energy's IEEE-754 bit pattern as the candidate's
+// key in keys[query][|E|].  Energies are sums of fabs() or squares, so >= +0,
+// and unsigned order of the patterns is numeric order.
+//
+// * predict_mask_kernel overwrites the keys of the known candidates with ~0:
+//   the host lists them per distinct (e, r, side) from the filter triples
+//   (predict_host.hpp), so no hash set is probed per (query, candidate).
+// * predict_select_kernel, one 256-thread workgroup per query: the key row is
+//   staged in LDS while it is small enough to leave four workgroups a CU, else
+//   re-read from L2 on every pass (FB15k's 120 KB row fits the 160 KB, but
+//   one workgroup a CU measured 3.2x slower); an 8-bit radix select from the top digit
+//   narrows a prefix around the k-th smallest key (256-bin LDS histogram, the
+//   lanes of a wave that share a digit add once) until the keys at or below
+//   the prefix fit the sort buffer; those are compacted in id order -- every
+//   key below the prefix, keys on it in ascending id until there are enough --
+//   and bitonic-sorted on (key, id) in LDS.  No communication between
+//   workgroups, no waiting on other work, no device-side allocation.
+//
+// The key buffer holds a bounded chunk of queries (<= 1 GiB), so a whole test
+// set's queries never need nq x |E| at once.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdlib>
+#include <limits>
+#include <numeric>
+#include <stdexcept>
+#include <vector>
+
+#include "eval_shared.hpp"
+#include "hip_util.hpp"
+#include "kernels_common.hpp"
+#include "predict.hpp"
+#include "predict_host.hpp"
+
+namespace kb2e {
+namespace {
+
+constexpr uint64_t kMasked = ~0ull;
+
+// ------------------------------------------------------------ candidate keys
+
+struct ScoreArgs {
+    const double* PT;    // [n][ne]
+    const double* relv;  // [n]
+    int32_t n, ne, l1;
+    const int32_t* qe;     // the known entity of each query of this relation
+    const int32_t* qside;  // 1: candidates are tails, 0: heads
+    int32_t nq;
+    uint64_t* keys;  // [nq][ne]
+};
+
+// grid.x: entity blocks of 256; grid.y: query tiles of kQ.  Dynamic LDS: P(e)
+// of the tile's queries [kQ][n] + r [n]; kRowsInLds false reads them from the
+// projection table (L1 / L2 broadcast), as eval_rank_kernel does.
+template <bool kRowsInLds>
+__global__ __launch_bounds__(256) void predict_score_kernel(ScoreArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* kr = lds;
+    double* rv = kr + kQ * a.n;
+    const int q0 = blockIdx.y * kQ;
+    const int nq = min(kQ, a.nq - q0);
+    if constexpr (kRowsInLds) {
+        for (int x = threadIdx.x; x < kQ * a.n; x += blockDim.x) {
+            const int q = x / a.n, k = x % a.n;
+            if (q < nq) kr[x] = a.PT[(int64_t)k * a.ne + a.qe[q0 + q]];
+        }
+        for (int k = threadIdx.x; k < a.n; k += blockDim.x) rv[k] = a.relv[k];
+    }
+    int qev[kQ];
+    bool tailq[kQ];
+#pragma unroll
+    for (int q = 0; q < kQ; ++q) {
+        qev[q] = q < nq ? a.qe[q0 + q] : 0;
+        tailq[q] = q < nq ? a.qside[q0 + q] != 0 : false;
+    }
+    __syncthreads();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.ne) return;
+    double e[kQ];
+#pragma unroll
+    for (int q = 0; q < kQ; ++q) e[q] = 0;
+    for (int k = 0; k < a.n; ++k) {
+        const double* col = a.PT + (int64_t)k * a.ne;
+        const double v = col[i];
+        const double r = kRowsInLds ? rv[k] : a.relv[k];
+#pragma unroll
+        for (int q = 0; q < kQ; ++q) {
+            const double p = kRowsInLds ? kr[q * a.n + k] : col[qev[q]];
+            // (P(x) - P(h)) - r with x the tail, (P(t) - P(x)) - r with x the head
+            const double d = tailq[q] ? v - p - r : p - v - r;
+            e[q] += a.l1 ? fabs(d) : d * d;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kQ; ++q)
+        if (q < nq) a.keys[(int64_t)(q0 + q) * a.ne + i] = (uint64_t)__double_as_longlong(e[q]);
+}
+
+struct MaskArgs {
+    uint64_t* keys;  // [rows][ne]
+    int32_t ne;
+    const int32_t* group;  // [rows]
+    const int64_t* off;
+    const int32_t* ids;
+};
+
+// One block per query row: the known candidates of its (e, r, side) get the key ~0.
+__global__ __launch_bounds__(256) void predict_mask_kernel(MaskArgs a) {
+    const int g = a.group[blockIdx.x];
+    uint64_t* row = a.keys + (int64_t)blockIdx.x * a.ne;
+    for (int64_t j = a.off[g] + threadIdx.x; j < a.off[g + 1]; j += blockDim.x) row[a.ids[j]] = kMasked;
+}
+
+// ------------------------------------------------------------ selection
+
+constexpr int kSelThreads = 256;
+constexpr int kSelCap = kPredictMaxK;  // sort buffer, in pairs
+constexpr int kSelMinCap = 256;        // narrow until this many pairs (or k, if larger) remain
+// scratch: keys [1024] u64, ids [1024] i32, histogram [256] u32, wave totals [2][4][2] u32, misc [8] u32
+constexpr size_t kSelOffIds = (size_t)kSelCap * 8;
+constexpr size_t kSelOffHist = kSelOffIds + (size_t)kSelCap * 4;
+constexpr size_t kSelOffWtot = kSelOffHist + 256 * 4;
+constexpr size_t kSelOffMisc = kSelOffWtot + 16 * 4;
+constexpr size_t kSelScratchBytes = kSelOffMisc + 16 * 4;
+static_assert(kSelScratchBytes % 16 == 0, "the key row behind the scratch is 8-byte data");
+
+struct SelectArgs {
+    const uint64_t* keys;  // [rows][ne]
+    int32_t ne, k;
+    int32_t* ids;    // [rows][k]
+    double* energy;  // [rows][k]
+    int32_t* found;  // [rows]
+};
+
+template <bool kRowLds>
+__global__ __launch_bounds__(kSelThreads) void predict_select_kernel(SelectArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
+    uint64_t* skey = (uint64_t*)sm;
+    int32_t* sid = (int32_t*)(sm + kSelOffIds);
+    uint32_t* hist = (uint32_t*)(sm + kSelOffHist);
+    uint32_t* wtot = (uint32_t*)(sm + kSelOffWtot);
+    uint32_t* misc = (uint32_t*)(sm + kSelOffMisc);
+    uint64_t* lrow = (uint64_t*)(sm + kSelScratchBytes);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int ne = a.ne;
+    const uint64_t* grow = a.keys + (int64_t)blockIdx.x * ne;
+    const uint64_t* row = kRowLds ? lrow : grow;
+    const uint64_t below_lanes = (1ull << lane) - 1;
+
+    // stage the row, count the candidates left
+    uint32_t mine = 0;
+    for (int i = tid; i < ne; i += kSelThreads) {
+        const uint64_t key = grow[i];
+        if constexpr (kRowLds) lrow[i] = key;
+        mine += key != kMasked;
+    }
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o);
+    if (lane == 0) misc[4 + wv] = mine;  // (slots no later phase writes)
+    __syncthreads();
+    const int valid = (int)(misc[4] + misc[5] + misc[6] + misc[7]);
+    const int kk = min(a.k, valid);
+    int32_t* oid = a.ids + (int64_t)blockIdx.x * a.k;
+    double* oen = a.energy + (int64_t)blockIdx.x * a.k;
+    if (tid == 0) a.found[blockIdx.x] = kk;
+    if (kk == 0) {  // (block-uniform)
+        for (int j = tid; j < a.k; j += kSelThreads) {
+            oid[j] = -1;
+            oen[j] = INFINITY;
+        }
+        return;
+    }
+
+    // radix select: (prefix, pmask) closes in on the kk-th smallest key.  `below`
+    // keys are under the prefix, `c` keys on it (the masked ones too while pmask
+    // is 0), and the kk-th is the remaining-th of those.
+    const uint32_t cap = (uint32_t)max(kk, kSelMinCap);
+    uint64_t prefix = 0, pmask = 0;
+    uint32_t below = 0, remaining = (uint32_t)kk, c = (uint32_t)ne;
+    for (int shift = 56; shift >= 0 && below + c > cap; shift -= 8) {
+        hist[tid] = 0;
+        __syncthreads();
+        for (int base = 0; base < ne; base += kSelThreads) {
+            const int i = base + tid;
+            bool act = false;
+            uint32_t dg = 0;
+            if (i < ne) {
+                const uint64_t key = row[i];
+                act = (key & pmask) == prefix;
+                dg = (uint32_t)(key >> shift) & 255u;
+            }
+            if (__ballot(act) == 0) continue;  // (wave-uniform)
+            // the lanes that hold the same digit add to its bin once
+            uint64_t peers = __ballot(act);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const bool bit = (dg >> b) & 1u;
+                const uint64_t bal = __ballot(act && bit);
+                peers &= bit ? bal : ~bal;
+            }
+            if (act && lane == __ffsll((long long)peers) - 1) atomicAdd(&hist[dg], (uint32_t)__popcll(peers));
+        }
+        __syncthreads();
+        // the bin that holds the remaining-th key: inclusive scan of the 256 bins
+        const uint32_t h = hist[tid];
+        uint32_t incl = h;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t up = __shfl_up(incl, o);
+            if (lane >= o) incl += up;
+        }
+        if (lane == 63) wtot[wv] = incl;
+        __syncthreads();
+        for (int w = 0; w < wv; ++w) incl += wtot[w];
+        const uint32_t excl = incl - h;
+        if (excl < remaining && remaining <= incl) {
+            misc[0] = (uint32_t)tid;
+            misc[1] = excl;
+            misc[2] = h;
+        }
+        __syncthreads();
+        const uint32_t bin = misc[0], before = misc[1];
+        c = misc[2];
+        below += before;
+        remaining -= before;
+        prefix |= (uint64_t)bin << shift;
+        pmask |= 0xFFull << shift;
+    }
+    // every key on the prefix when they fit; else (all digits fixed: equal keys)
+    // the first `remaining` of them by id
+    const uint32_t need_eq = below + c <= cap ? c : remaining;
+
+    // compaction in id order: keys under the prefix to [0, below), keys on it
+    // behind them; never a masked key
+    uint32_t run_l = 0, run_e = 0;
+    int it = 0;
+    for (int base = 0; base < ne; base += kSelThreads, ++it) {
+        const int i = base + tid;
+        bool L = false, E = false;
+        uint64_t key = 0;
+        if (i < ne) {
+            key = row[i];
+            if (key != kMasked) {
+                const uint64_t mk = key & pmask;
+                L = mk < prefix;
+                E = mk == prefix;
+            }
+        }
+        const uint64_t mL = __ballot(L), mE = __ballot(E);
+        uint32_t* wt = wtot + (it & 1) * 8;
+        if (lane == 0) {
+            wt[wv * 2] = (uint32_t)__popcll(mL);
+            wt[wv * 2 + 1] = (uint32_t)__popcll(mE);
+        }
+        __syncthreads();
+        uint32_t off_l = run_l, off_e = run_e;
+#pragma unroll
+        for (int w = 0; w < kSelThreads / 64; ++w) {
+            const uint32_t cl = wt[w * 2], ce = wt[w * 2 + 1];
+            if (w < wv) {
+                off_l += cl;
+                off_e += ce;
+            }
+            run_l += cl;
+            run_e += ce;
+        }
+        if (L) {
+            const uint32_t pos = off_l + (uint32_t)__popcll(mL & below_lanes);
+            if (pos < (uint32_t)kSelCap) {
+                skey[pos] = key;
+                sid[pos] = i;
+            }
+        }
+        if (E) {
+            const uint32_t rk = off_e + (uint32_t)__popcll(mE & below_lanes);
+            const uint32_t pos = below + rk;
+            if (rk < need_eq && pos < (uint32_t)kSelCap) {
+                skey[pos] = key;
+                sid[pos] = i;
+            }
+        }
+    }
+    const int nsel = (int)min(below + min(run_e, need_eq), (uint32_t)kSelCap);
+    int P = 2;
+    while (P < nsel) P <<= 1;
+    for (int i = nsel + tid; i < P; i += kSelThreads) {
+        skey[i] = kMasked;
+        sid[i] = INT_MAX;
+    }
+    __syncthreads();
+    // bitonic sort of the P pairs on (key, id)
+    for (int size = 2; size <= P; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = tid; t < P / 2; t += kSelThreads) {
+                const int lo = 2 * t - (t & (stride - 1));
+                const int hi = lo + stride;
+                const uint64_t ka = skey[lo], kb = skey[hi];
+                const int32_t ia = sid[lo], ib = sid[hi];
+                const bool gt = ka > kb || (ka == kb && ia > ib);
+                const bool asc = (lo & size) == 0;
+                if (gt == asc) {
+                    skey[lo] = kb;
+                    skey[hi] = ka;
+                    sid[lo] = ib;
+                    sid[hi] = ia;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int j = tid; j < a.k; j += kSelThreads) {
+        const bool have = j < kk;
+        oid[j] = have ? sid[j] : -1;
+        oen[j] = have ? __longlong_as_double((long long)skey[j]) : (double)INFINITY;
+    }
+}
+
+// ------------------------------------------------------------ triple energies
+
+template <typename T>
+struct TripleArgs {
+    int32_t model, n, ld, l1;
+    const T* ent;
+    const T* rel;
+    const T* w;
+    const int32_t *h, *t, *r;
+    int32_t count;
+    double* out;
+};
+
+// TransE (transe/transe.cpp) and TransH (transh/transh.cpp:10-29): one thread
+// per triple, the reference's serial loops in FP64.
+template <typename T>
+__global__ __launch_bounds__(256) void score_triples_kernel(TripleArgs<T> a) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= a.count) return;
+    const T* h = a.ent + (int64_t)a.h[x] * a.ld;
+    const T* t = a.ent + (int64_t)a.t[x] * a.ld;
+    const T* r = a.rel + (int64_t)a.r[x] * a.ld;
+    double e = 0;
+    if (a.model == 0) {
+        for (int k = 0; k < a.n; ++k) {
+            const double d = (double)t[k] - (double)h[k] - (double)r[k];
+            e += a.l1 ? fabs(d) : d * d;
+        }
+    } else {
+        const T* w = a.w + (int64_t)a.r[x] * a.ld;
+        double hs = 0, ts = 0;
+        for (int k = 0; k < a.n; ++k) {
+            hs += (double)w[k] * (double)h[k];
+            ts += (double)w[k] * (double)t[k];
+        }
+        for (int k = 0; k < a.n; ++k)
+            e += fabs((double)t[k] - ts * (double)w[k] - ((double)h[k] - hs * (double)w[k]) - (double)r[k]);
+    }
+    a.out[x] = e;
+}
+
+// TransR (transr/transr.cpp:13-37, zeroed work vectors): one wave per triple.
+// Lane i (+64c) accumulates headVec[i] and tailVec[i] over j in order from
+// zero; the terms go through LDS and lane 0 adds them over i in order.
+// Dynamic LDS: [waves][n] doubles.
+template <typename T>
+__global__ __launch_bounds__(256) void score_triples_transr_kernel(TripleArgs<T> a) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int wv = threadIdx.x >> 6, l = lane_id();
+    const int x = blockIdx.x * (blockDim.x >> 6) + wv;
+    if (x >= a.count) return;  // (wave-uniform; no workgroup barrier below)
+    double* term = lds + (size_t)wv * a.n;
+    const T* h = a.ent + (int64_t)a.h[x] * a.ld;
+    const T* t = a.ent + (int64_t)a.t[x] * a.ld;
+    const T* r = a.rel + (int64_t)a.r[x] * a.ld;
+    const T* W = a.w + (int64_t)a.r[x] * a.n * a.ld;
+    for (int i = l; i < a.n; i += 64) {
+        double hv = 0, tv = 0;
+        for (int j = 0; j < a.n; ++j) {
+            const double w = (double)W[(int64_t)j * a.ld + i];
+            hv += w * (double)h[j];
+            tv += w * (double)t[j];
+        }
+        const double d = tv - hv - (double)r[i];
+        term[i] = a.l1 ? fabs(d) : d * d;
+    }
+    wave_lds_sync();
+    if (l == 0) {
+        double e = 0;
+        for (int i = 0; i < a.n; ++i) e += term[i];
+        a.out[x] = e;
+    }
+}
+
+// ------------------------------------------------------------ host side
+
+struct Span {
+    const PredictHooks* h;
+    const char* name;
+    hipEvent_t a = nullptr;
+    Span(const PredictHooks* hooks, const char* nm) : h(hooks), name(nm) {
+        if (h && h->begin) a = h->begin(h->ud);
+    }
+    void end() {
+        if (h && h->end && a) h->end(h->ud, name, a);
+        a = nullptr;
+    }
+};
+
+bool env_on(const char* name) {
+    const char* v = getenv(name);
+    return v && v[0] == '1';
+}
+
+template <typename T>
+void run_score_triples(const EvalTables& t, const int32_t* dh, const int32_t* dt, const int32_t* dr, int32_t count,
+                       double* dout) {
+    TripleArgs<T> a{t.model, t.n, t.ld, t.l1, (const T*)t.ent, (const T*)t.rel, (const T*)t.w, dh, dt, dr, count, dout};
+    if (t.model == 2) {
+        const size_t lds = (size_t)4 * t.n * 8;
+        score_triples_transr_kernel<T><<<(count + 3) / 4, 256, lds, t.stream>>>(a);
+    } else {
+        score_triples_kernel<T><<<(count + 255) / 256, 256, 0, t.stream>>>(a);
+    }
+    HIPCHK(hipGetLastError());
+}
+
+}  // namespace
+
+void score_triples(const EvalTables& t, const int32_t* heads, const int32_t* tails, const int32_t* relations,
+                   int64_t count, double* energy) {
+    if (count < 1) throw std::invalid_argument("no triples to score");
+    for (int64_t k = 0; k < count; ++k)
+        if (heads[k] < 0 || heads[k] >= t.ne || tails[k] < 0 || tails[k] >= t.ne || relations[k] < 0 ||
+            relations[k] >= t.nr)
+            throw std::invalid_argument("triple " + std::to_string(k) + " has an id out of range");
+    const int64_t chunk = std::min<int64_t>(count, (int64_t)1 << 22);
+    DevBuf d_h, d_t, d_r, d_out;
+    d_h.alloc((size_t)chunk * 4);
+    d_t.alloc((size_t)chunk * 4);
+    d_r.alloc((size_t)chunk * 4);
+    d_out.alloc((size_t)chunk * 8);
+    for (int64_t c0 = 0; c0 < count; c0 += chunk) {
+        const int32_t m = (int32_t)std::min(chunk, count - c0);
+        HIPCHK(hipMemcpyAsync(d_h.p, heads + c0, (size_t)m * 4, hipMemcpyHostToDevice, t.stream));
+        HIPCHK(hipMemcpyAsync(d_t.p, tails + c0, (size_t)m * 4, hipMemcpyHostToDevice, t.stream));
+        HIPCHK(hipMemcpyAsync(d_r.p, relations + c0, (size_t)m * 4, hipMemcpyHostToDevice, t.stream));
+        if (t.f64) run_score_triples<double>(t, d_h.as<int32_t>(), d_t.as<int32_t>(), d_r.as<int32_t>(), m, d_out.as<double>());
+        else run_score_triples<float>(t, d_h.as<int32_t>(), d_t.as<int32_t>(), d_r.as<int32_t>(), m, d_out.as<double>());
+        HIPCHK(hipMemcpyAsync(energy + c0, d_out.p, (size_t)m * 8, hipMemcpyDeviceToHost, t.stream));
+        HIPCHK(hipStreamSynchronize(t.stream));
+    }
+}
+
+void predict_topk(const EvalTables& t, const PredictQuery& q, int32_t* ids, double* energy, int32_t* found,
+                  const PredictHooks* hooks) {
+    const int ne = t.ne, n = t.n, k = q.k;
+    if (q.nq < 1) throw std::invalid_argument("no queries");
+    if (q.nq > INT32_MAX) throw std::invalid_argument("too many queries in one call");
+    if (k < 1 || k > kPredictMaxK) throw std::invalid_argument("k must be in 1.." + std::to_string(kPredictMaxK));
+    for (int64_t x = 0; x < q.nq; ++x) {
+        if (q.side[x] != 0 && q.side[x] != 1) throw std::invalid_argument("query side must be 0 (head) or 1 (tail)");
+        if (q.ent[x] < 0 || q.ent[x] >= ne || q.rel[x] < 0 || q.rel[x] >= t.nr)
+            throw std::invalid_argument("query " + std::to_string(x) + " has an id out of range");
+    }
+    for (int64_t x = 0; x < q.nfilter; ++x)
+        if (q.fh[x] < 0 || q.fh[x] >= ne || q.ft[x] < 0 || q.ft[x] >= ne || q.fr[x] < 0 || q.fr[x] >= t.nr)
+            throw std::invalid_argument("filter triple out of range");
+    const int64_t nq = q.nq;
+
+    // queries grouped by relation (stable: the caller's order within one)
+    std::vector<int64_t> order((size_t)nq);
+    std::iota(order.begin(), order.end(), (int64_t)0);
+    std::stable_sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return q.rel[x] < q.rel[y]; });
+    const KnownCandidates kc =
+        build_known_candidates(q.ent, q.rel, q.side, nq, q.fh, q.ft, q.fr, q.nfilter, t.nr);
+    std::vector<int32_t> se((size_t)nq), ss((size_t)nq), sg((size_t)nq), srel((size_t)nq);
+    for (int64_t x = 0; x < nq; ++x) {
+        se[x] = q.ent[order[x]];
+        ss[x] = q.side[order[x]];
+        sg[x] = kc.group[(size_t)order[x]];
+        srel[x] = q.rel[order[x]];
+    }
+
+    // rows of the key buffer: <= 1 GiB (KB2E_PREDICT_CHUNK_ROWS caps it further: tests)
+    int64_t rows = std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)ne * 8));
+    if (const char* cr = getenv("KB2E_PREDICT_CHUNK_ROWS")) {
+        const long v = atol(cr);
+        if (v >= 1) rows = std::min<int64_t>(rows, v);
+    }
+    rows = std::min(rows, nq);
+    // n <= 1200 fits; KB2E_EVAL_ROWS_L2=1 forces the L2 form as in the evaluator
+    const bool rows_lds = (size_t)(kQ + 1) * n * 8 <= kLdsMax && !env_on("KB2E_EVAL_ROWS_L2");
+    const size_t score_lds = rows_lds ? (size_t)(kQ + 1) * n * 8 : 0;
+    // the key row in LDS while that still leaves four workgroups a CU (|E| <= 3,400);
+    // a larger row is re-read from L2 -- at FB15k's 120 KB one workgroup a CU made the
+    // selection 3.2x slower than the L2 form.  KB2E_PREDICT_KEYS_L2=1
+    // forces the L2 form, =0 the LDS form whenever the row fits the 160 KB (tests)
+    const size_t staged = kSelScratchBytes + (size_t)ne * 8;
+    const char* kl2 = getenv("KB2E_PREDICT_KEYS_L2");
+    bool keys_lds = staged <= kLdsMax / 4;
+    if (kl2 && kl2[0] == '1') keys_lds = false;
+    if (kl2 && kl2[0] == '0') keys_lds = staged <= kLdsMax;
+    const size_t select_lds = kSelScratchBytes + (keys_lds ? (size_t)ne * 8 : 0);
+    if (rows_lds) allow_lds(predict_score_kernel<true>, score_lds);
+    if (keys_lds) allow_lds(predict_select_kernel<true>, select_lds);
+
+    DevBuf d_e, d_s, d_g, d_off, d_kid, d_keys, d_PT, d_relv, d_ids, d_en, d_found;
+    d_e.alloc((size_t)nq * 4);
+    d_s.alloc((size_t)nq * 4);
+    d_g.alloc((size_t)nq * 4);
+    d_off.alloc(kc.off.size() * 8);
+    d_kid.alloc(kc.ids.size() * 4);
+    HIPCHK(hipMemcpyAsync(d_e.p, se.data(), (size_t)nq * 4, hipMemcpyHostToDevice, t.stream));
+    HIPCHK(hipMemcpyAsync(d_s.p, ss.data(), (size_t)nq * 4, hipMemcpyHostToDevice, t.stream));
+    HIPCHK(hipMemcpyAsync(d_g.p, sg.data(), (size_t)nq * 4, hipMemcpyHostToDevice, t.stream));
+    HIPCHK(hipMemcpyAsync(d_off.p, kc.off.data(), kc.off.size() * 8, hipMemcpyHostToDevice, t.stream));
+    if (!kc.ids.empty())
+        HIPCHK(hipMemcpyAsync(d_kid.p, kc.ids.data(), kc.ids.size() * 4, hipMemcpyHostToDevice, t.stream));
+    d_keys.alloc((size_t)rows * ne * 8);
+    d_PT.alloc((size_t)n * ne * 8);
+    d_relv.alloc((size_t)n * 8);
+    d_ids.alloc((size_t)rows * k * 4);
+    d_en.alloc((size_t)rows * k * 8);
+    d_found.alloc((size_t)rows * 4);
+    std::vector<int32_t> hids((size_t)rows * k), hfound((size_t)rows);
+    std::vector<double> hen((size_t)rows * k);
+
+    int cur_rel = -1;  // the relation d_PT holds (a relation's queries may span two chunks)
+    for (int64_t c0 = 0; c0 < nq; c0 += rows) {
+        const int64_t c1 = std::min(nq, c0 + rows);
+        {
+            Span sp(hooks, "predict_score");
+            for (int64_t a0 = c0; a0 < c1;) {
+                const int r = srel[a0];
+                int64_t a1 = a0;
+                while (a1 < c1 && srel[a1] == r) ++a1;
+                if (r != cur_rel) {
+                    project_any(t, r, d_PT.as<double>(), d_relv.as<double>());
+                    cur_rel = r;
+                }
+                ScoreArgs sa{d_PT.as<double>(), d_relv.as<double>(), n, ne, t.l1, d_e.as<int32_t>() + a0,
+                             d_s.as<int32_t>() + a0, (int32_t)(a1 - a0), d_keys.as<uint64_t>() + (a0 - c0) * ne};
+                dim3 grid((ne + 255) / 256, (unsigned)((a1 - a0 + kQ - 1) / kQ));
+                if (rows_lds) predict_score_kernel<true><<<grid, 256, score_lds, t.stream>>>(sa);
+                else predict_score_kernel<false><<<grid, 256, 0, t.stream>>>(sa);
+                HIPCHK(hipGetLastError());
+                a0 = a1;
+            }
+            sp.end();
+        }
+        const unsigned m = (unsigned)(c1 - c0);
+        if (!kc.ids.empty()) {
+            Span sp(hooks, "predict_mask");
+            MaskArgs ma{d_keys.as<uint64_t>(), ne, d_g.as<int32_t>() + c0, d_off.as<int64_t>(), d_kid.as<int32_t>()};
+            predict_mask_kernel<<<m, 256, 0, t.stream>>>(ma);
+            HIPCHK(hipGetLastError());
+            sp.end();
+        }
+        {
+            Span sp(hooks, "predict_select");
+            SelectArgs sa{d_keys.as<uint64_t>(), ne, k, d_ids.as<int32_t>(), d_en.as<double>(), d_found.as<int32_t>()};
+            if (keys_lds) predict_select_kernel<true><<<m, kSelThreads, select_lds, t.stream>>>(sa);
+            else predict_select_kernel<false><<<m, kSelThreads, select_lds, t.stream>>>(sa);
+            HIPCHK(hipGetLastError());
+            sp.end();
+        }
+        HIPCHK(hipMemcpyAsync(hids.data(), d_ids.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, t.stream));
+        HIPCHK(hipMemcpyAsync(hen.data(), d_en.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, t.stream));
+        HIPCHK(hipMemcpyAsync(hfound.data(), d_found.p, (size_t)m * 4, hipMemcpyDeviceToHost, t.stream));
+        HIPCHK(hipStreamSynchronize(t.stream));
+        for (int64_t x = c0; x < c1; ++x) {  // back to the caller's order
+            const int64_t o = order[x];
+            std::copy_n(hids.data() + (x - c0) * k, k, ids + o * k);
+            std::copy_n(hen.data() + (x - c0) * k, k, energy + o * k);
+            found[o] = hfound[x - c0];
+        }
+    }
+}
+
+}  // namespace kb2e

@@ -1,0 +1,43 @@
+// predict.hpp -- using a trained model on the device: the energy of given
+// triples and the top-k candidates of one-sided queries.  Its own translation
+// unit (predict.hip) behind kb2e_score_triples / kb2e_predict; the stateless
+// FP64 energies are the evaluator's (eval.hpp, eval_shared.hpp).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "eval.hpp"
+
+namespace kb2e {
+
+// Timing of the kernel families (the engine's profile): begin() returns the
+// start event of a span on the tables' stream (null when profiling is off),
+// end() records its stop event under `name`.
+struct PredictHooks {
+    void* ud;
+    hipEvent_t (*begin)(void* ud);
+    void (*end)(void* ud, const char* name, hipEvent_t a);
+};
+
+struct PredictQuery {
+    const int32_t *ent, *rel, *side;  // query q: (ent[q], ?, rel[q]) for side 1, (?, ent[q], rel[q]) for side 0
+    int64_t nq;
+    int32_t k;                        // 1..kPredictMaxK
+    const int32_t *fh, *ft, *fr;      // candidates whose triple is listed here are excluded
+    int64_t nfilter;
+};
+
+constexpr int kPredictMaxK = 1024;
+
+// ids / energy [nq][k], found [nq]: per query the found = min(k, |E| - excluded)
+// candidates of smallest energy in ascending (energy, id) order, then -1 / +inf.
+void predict_topk(const EvalTables& t, const PredictQuery& q, int32_t* ids, double* energy, int32_t* found,
+                  const PredictHooks* hooks = nullptr);
+
+// energy[i] = tripleEnergy(heads[i], tails[i], relations[i]) (TransR from zeroed work vectors).
+void score_triples(const EvalTables& t, const int32_t* heads, const int32_t* tails, const int32_t* relations,
+                   int64_t count, double* energy);
+
+}  // namespace kb2e

@@ -28,7 +28,8 @@ EXPORTS = [
     "kb2e_device_bytes", "kb2e_device_tables", "kb2e_renormalize", "kb2e_evaluate", "kb2e_evaluate_transr_compat",
     "kb2e_renormalize_rows", "kb2e_init_params_device", "kb2e_write_table", "kb2e_format_table",
     "kb2e_read_table", "kb2e_comm_unique_id", "kb2e_comm_init_rank", "kb2e_comm_init_group", "kb2e_merge_epoch",
-    "kb2e_merge_epoch_group", "kb2e_comm_info", "kb2e_get_config",
+    "kb2e_merge_epoch_group", "kb2e_comm_info", "kb2e_get_config", "kb2e_score_triples", "kb2e_predict",
+    "kb2e_rank_triples",
 ]
 COMM_ID_BYTES = 128
 READ_VERBATIM, READ_UNIT, READ_SHRINK = 0, 1, 2
@@ -89,6 +90,9 @@ def lib():
             "kb2e_evaluate": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, dp]),
             "kb2e_evaluate_transr_compat": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, dp, dp, vp,
                                                   vp]),
+            "kb2e_score_triples": (i32, [vp, i32p, i32p, i32p, i64, dp]),
+            "kb2e_predict": (i32, [vp, i32p, i32p, i32p, i64, i32, i32p, i32p, i32p, i64, i32p, dp, i32p]),
+            "kb2e_rank_triples": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, C.POINTER(i64)]),
             "kb2e_comm_unique_id": (i32, [u8p]),
             "kb2e_comm_init_rank": (i32, [vp, i32, i32, u8p]),
             "kb2e_comm_init_group": (i32, [C.POINTER(vp), i32]),
@@ -340,6 +344,58 @@ class Engine:
                                                       _dp(out), None, None), "evaluate_transr_compat")
         return {"raw_rank": out[0], "raw_hits10": out[1], "filtered_rank": out[2], "filtered_hits10": out[3],
                 "ties": int(out[4]), "work": w.reshape(2, self.n)}
+
+    # ------------------------------------------------ using a trained model
+    @staticmethod
+    def _filter_cols(filt):
+        if filt is None or len(filt) == 0:
+            return [None, None, None], 0
+        filt = np.ascontiguousarray(filt, dtype=np.int32)
+        cols = [np.ascontiguousarray(filt[:, k]) for k in range(3)]
+        return cols, len(filt)
+
+    def score(self, triples):
+        """Energy of each (head, tail, relation) row: float64[count], the reference's
+        tripleEnergy bit for bit (TransR from zeroed work vectors)."""
+        t = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+        cols = [np.ascontiguousarray(t[:, k]) for k in range(3)]
+        out = np.zeros(len(t))
+        self._check(lib().kb2e_score_triples(self.h, _ip(cols[0]), _ip(cols[1]), _ip(cols[2]), len(t), _dp(out)),
+                    "score_triples")
+        return out
+
+    def predict(self, entities, relations, side, k, filt=None):
+        """Top-k candidates of one-sided queries: side 1 asks for the tails of
+        (entity, ?, relation), side 0 for the heads of (?, entity, relation);
+        candidates whose triple is a row of `filt` are excluded.  Returns
+        (ids int32[nq, k], energy float64[nq, k], found int32[nq]): ascending
+        (energy, id), padded with -1 / +inf after found[q]."""
+        e = np.ascontiguousarray(entities, dtype=np.int32).reshape(-1)
+        r = np.ascontiguousarray(relations, dtype=np.int32).reshape(-1)
+        s = np.ascontiguousarray(side, dtype=np.int32).reshape(-1)
+        if not (len(e) == len(r) == len(s)):
+            raise ValueError("entities, relations and side differ in length")
+        nq, k = len(e), int(k)
+        fc, nf = self._filter_cols(filt)
+        kk = max(k, 1)
+        ids = np.full((nq, kk), -1, np.int32)
+        en = np.full((nq, kk), np.inf)
+        found = np.zeros(nq, np.int32)
+        self._check(lib().kb2e_predict(self.h, _ip(e), _ip(r), _ip(s), nq, k, *[None if c is None else _ip(c) for c in fc],
+                                       nf, _ip(ids), _dp(en), _ip(found)), "predict")
+        return ids, en, found
+
+    def rank_triples(self, test, filt):
+        """evaluate()'s ranks per test triple, in the caller's order: int64[ntest, 4] =
+        head raw, head filtered, tail raw, tail filtered."""
+        test = np.ascontiguousarray(test, dtype=np.int32)
+        tc = [np.ascontiguousarray(test[:, k]) for k in range(3)]
+        fc, nf = self._filter_cols(filt)
+        ranks = np.zeros((len(test), 4), np.int64)
+        self._check(lib().kb2e_rank_triples(self.h, _ip(tc[0]), _ip(tc[1]), _ip(tc[2]), len(test),
+                                            *[None if c is None else _ip(c) for c in fc], nf,
+                                            ranks.ctypes.data_as(C.POINTER(C.c_int64))), "rank_triples")
+        return ranks
 
     def device_bytes(self):
         return lib().kb2e_device_bytes(self.h)

@@ -13,6 +13,10 @@ format, exactly what ``trainTransR --seeddatadir`` reads.
 
 Used by tools/hits_parity.py (FB15k-shaped runs) and the schedule-parity GPU
 test (tests/test_gpu_hits_parity.py).
+
+``relation_categories`` / ``hits_by_category`` give the 1-1 / 1-N / N-1 / N-N
+Hits@k table of the TransE, TransH and TransR papers from the per-triple ranks
+of ``Engine.rank_triples``.
 """
 from __future__ import annotations
 
@@ -96,4 +100,49 @@ def schedule_parity(ds, model, dim, epochs, *, seed_epochs=0, test=None, schedul
         for k in ("filtered_hits10", "raw_hits10"):
             out[f"delta_{k}_pp"] = 100.0 * (out[b][k] - out[a][k])
         out["delta_filtered_rank"] = out[b]["filtered_rank"] - out[a]["filtered_rank"]
+    return out
+
+
+CATEGORIES = ("1-1", "1-N", "N-1", "N-N")
+
+
+def relation_categories(train, num_relations, threshold=1.5):
+    """Per relation: the mean number of tails per (head, relation) pair (tph) and
+    of heads per (tail, relation) pair (hpt) over the distinct training triples,
+    and its category with the 1.5 threshold of Bordes et al. (2013): "1-1" (both
+    below), "1-N" (tph at or above: many tails for a head), "N-1" (hpt at or
+    above), "N-N" (both).  A relation without training triples has means 0 and
+    counts as 1-1.  Returns (cats list[str], tph float64[R], hpt float64[R])."""
+    t = np.unique(np.asarray(train, dtype=np.int64).reshape(-1, 3), axis=0)
+    tph = np.zeros(num_relations)
+    hpt = np.zeros(num_relations)
+    for r in range(num_relations):
+        rows = t[t[:, 2] == r]
+        if len(rows):
+            tph[r] = len(rows) / len(np.unique(rows[:, 0]))
+            hpt[r] = len(rows) / len(np.unique(rows[:, 1]))
+    cats = []
+    for r in range(num_relations):
+        many_t, many_h = tph[r] >= threshold, hpt[r] >= threshold
+        cats.append("N-N" if many_t and many_h else "1-N" if many_t else "N-1" if many_h else "1-1")
+    return cats, tph, hpt
+
+
+def hits_by_category(ranks, test, cats, at=10):
+    """Filtered Hits@`at` per relation category and prediction side, from
+    ``Engine.rank_triples`` output (columns head raw, head filtered, tail raw,
+    tail filtered).  Returns {category: {"count", "head", "tail"}}; the
+    fractions are None for a category without test triples."""
+    ranks = np.asarray(ranks).reshape(-1, 4)
+    test = np.asarray(test).reshape(-1, 3)
+    if len(ranks) != len(test):
+        raise ValueError("ranks and test differ in length")
+    cat_of = np.array([CATEGORIES.index(cats[r]) for r in test[:, 2]], dtype=np.int64)
+    out = {}
+    for c, name in enumerate(CATEGORIES):
+        sel = cat_of == c
+        m = int(sel.sum())
+        out[name] = {"count": m,
+                     "head": float((ranks[sel, 1] <= at).mean()) if m else None,
+                     "tail": float((ranks[sel, 3] <= at).mean()) if m else None}
     return out
