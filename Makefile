@@ -105,7 +105,7 @@ ref:
 # stream (tests/native/host_check.cpp), the text formatter / parser, the Bloom
 # prefilter.  GPU box: libkb2e_san.so, the engine with its host code instrumented
 # (-Xarch_host: the device code is not), and the CLI on it (bin/san/train*, eval*),
-# run by tools/gpu_sanitize.sh over the golden tiny set (training, the in-process
+# to be run by hand over the golden tiny set (training, the in-process
 # two-context merge, the evaluator, the text tables).
 SANFLAGS := -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all
 HIPSAN := $(foreach f,-fsanitize=address -fsanitize=undefined -fno-sanitize-recover=all -fno-omit-frame-pointer,-Xarch_host $(f))

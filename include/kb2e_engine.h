@@ -110,8 +110,9 @@ const char* kb2e_last_error(const kb2e_ctx* ctx);
  * per-relation head/tail co-occurrence means of Trainer::loadFiles
  * (common/trainer.cpp:26-32, 151-201).  Builds the negative-sample filter and
  * the Bernoulli table on the device.  Contexts take dim <= 512 for every
- * model and schedule, checked at kb2e_create (KB2E_EUNSUPPORTED above); wide
- * TransR keeps a relation's matrix in L2 instead of LDS. */
+ * model and schedule, PARALLEL TransR included (above 128 on the wide
+ * kernels), checked at kb2e_create (KB2E_EINVAL above); wide TransR keeps a
+ * relation's matrix in L2 instead of LDS. */
 kb2e_status kb2e_upload_triples(kb2e_ctx* ctx, const int32_t* heads, const int32_t* tails,
                                 const int32_t* relations, int64_t count);
 

@@ -1098,6 +1098,10 @@ void setup_buffers(kb2e_ctx* c) {
     c->n = g.dim;
     c->ld = (g.dim + 1) & ~1;
     c->ch = (g.dim + kWave * kVec - 1) / (kWave * kVec);
+    // the row kernels are built for 1, 2 and 4 chunks a lane: three chunks (257 <= dim <= 384)
+    // run the four-chunk build, which writes and reads CH * kVec sign words an update -- the
+    // stride of xbits must be that build's, or an update's last words land on the next one's
+    if (c->ch == 3) c->ch = 4;
     c->nw = c->ch * kVec;
     const size_t es = (size_t)c->esize;
     c->ent.alloc((size_t)g.num_entities * c->ld * es);

@@ -143,13 +143,15 @@ long long orc_site_iterations(int site) { return (site >= 0 && site < 4) ? g_sit
 
 /* transr/trainer.cpp:35-64; b is n x n with b[j*n+i] = weights[j][i]. */
 void orc_transr_norm(double* a, double* b, int n, double rate) {
+    double proj[n];
     while (1) {
+        /* x = |b^T a|^2: every column sum over j in order, as the reference's loop nest
+         * with i outside; rows walked contiguously (same sums bit for bit) */
         double x = 0;
-        for (int i = 0; i < n; i++) {
-            double tmp = 0;
-            for (int j = 0; j < n; j++) tmp += b[j * n + i] * a[j];
-            x += sqr(tmp);
-        }
+        for (int i = 0; i < n; i++) proj[i] = 0;
+        for (int j = 0; j < n; j++)
+            for (int i = 0; i < n; i++) proj[i] += b[j * n + i] * a[j];
+        for (int i = 0; i < n; i++) x += sqr(proj[i]);
         if (x <= 1) break;
         g_transr_norm_iters++;
         g_site_iters[g_site]++;
@@ -405,8 +407,9 @@ static double transr_energy(orc_model* m, const double* E, const double* R, cons
     if (!m->transr_compat) {
         for (int i = 0; i < n; i++) hv[i] = tv[i] = 0;
     }
-    for (int i = 0; i < n; i++) {
-        for (int j = 0; j < n; j++) {
+    /* (the reference nests i outside j; every hv[i], tv[i] still sums over j in order) */
+    for (int j = 0; j < n; j++) {
+        for (int i = 0; i < n; i++) {
             hv[i] += Wr[(size_t)j * n + i] * eh[j];
             tv[i] += Wr[(size_t)j * n + i] * et[j];
         }
@@ -491,20 +494,30 @@ static void transr_update(orc_model* m, int h, int t, int r, int corrupted) {
     const double* W = m->w + (size_t)r * n * n;
     double* Wn = m->w_next + (size_t)r * n * n;
     double *nr_ = ROW(m->rel_next, r), *nh = ROW(m->ent_next, h), *nt = ROW(m->ent_next, t);
+    /* The reference nests i outside j.  Here the rows of W are walked contiguously;
+     * every sum and every accumulation keeps its order (headSum / tailSum over j;
+     * nh[j], nt[j] over i, interleaved as there, which matters when h == t), so the
+     * results are the same bit for bit. */
+    double headSum[n], tailSum[n], xs[n];
+    for (int i = 0; i < n; i++) headSum[i] = tailSum[i] = 0;
+    for (int j = 0; j < n; j++) {
+        for (int i = 0; i < n; i++) {
+            headSum[i] += W[(size_t)j * n + i] * eh[j];
+            tailSum[i] += W[(size_t)j * n + i] * et[j];
+        }
+    }
     for (int i = 0; i < n; i++) {
-        double headSum = 0, tailSum = 0;
-        for (int j = 0; j < n; j++) {
-            headSum += W[(size_t)j * n + i] * eh[j];
-            tailSum += W[(size_t)j * n + i] * et[j];
-        }
-        double x = 2.0 * (tailSum - headSum - er[i]);
+        double x = 2.0 * (tailSum[i] - headSum[i] - er[i]);
         if (m->distance == 0) x = x > 0 ? 1 : -1;
-        for (int j = 0; j < n; j++) {
-            Wn[(size_t)j * n + i] -= beta * m->lr * x * (eh[j] - et[j]);
-            nh[j] -= beta * m->lr * x * W[(size_t)j * n + i];
-            nt[j] += beta * m->lr * x * W[(size_t)j * n + i];
-        }
+        xs[i] = x;
         nr_[i] -= beta * m->lr * x;
+    }
+    for (int j = 0; j < n; j++) {
+        for (int i = 0; i < n; i++) {
+            Wn[(size_t)j * n + i] -= beta * m->lr * xs[i] * (eh[j] - et[j]);
+            nh[j] -= beta * m->lr * xs[i] * W[(size_t)j * n + i];
+            nt[j] += beta * m->lr * xs[i] * W[(size_t)j * n + i];
+        }
     }
     orc_norm(nr_, n, 0);
     orc_norm(nh, n, 0);

@@ -334,7 +334,8 @@ def test_transr_parallel_wide_compat_scan(sub, prefix, monkeypatch):
 
 def test_transr_parallel_wide_fp32_close():
     """FP32 tables at n = 200 on the wide kernels: loss and active counts within 1 %
-    of the FP64 run over two epochs (FP32 hinge decisions flip at the margin)."""
+    of the FP64 run over two epochs (FP32 hinge decisions flip at the margin; the
+    element-wise check of the wide float kernels is per batch, test_gpu_fp32_step.py)."""
     ds = data.synthetic("small", seed=1)
     out = {}
     for prec in (64, 32):
@@ -361,7 +362,8 @@ def test_transr_parallel_refuses_above_512():
 def test_transr_parallel_fp32_chain_close(monkeypatch):
     """FP32 tables take the same pair-by-pair chain (double arithmetic, FP32
     storage): epoch loss and active counts within 1 % of the FP64 run, the tables
-    within FP32 rounding drift (median 1e-3)."""
+    within FP32 rounding drift (median 1e-3).  Element by element against the CPU
+    model, one batch at a time: test_gpu_fp32_step.py."""
     ds = data.synthetic("small", seed=1)
     out, tabs = {}, {}
     for prec in (64, 32):
@@ -380,7 +382,8 @@ def test_transr_parallel_fp32_chain_close(monkeypatch):
 
 
 def test_transr_parallel_fp32_close(monkeypatch):
-    """FP32 tables: hinge decisions flip at the margin, so statistics, not elements.
+    """FP32 tables: hinge decisions flip at the margin, so over epochs statistics, not
+    elements (per batch the elements are checked: test_gpu_fp32_step.py).
     (Both on the Jacobi transRNorm, which KB2E_RPAR_CONS=jacobi asks for by name; by
     default FP32 takes the generic pair-by-pair chain: test_transr_parallel_fp32_chain_close.)"""
     monkeypatch.setenv("KB2E_RPAR_CONS", "jacobi")

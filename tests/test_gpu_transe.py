@@ -84,6 +84,15 @@ def test_oracle_parity_small(dim, distance):
     _oracle_vs_engine(ds, dim, 2, distance=distance)
 
 
+@pytest.mark.parametrize("dim,distance", [(300, 0), (260, 0), (384, 0), (300, 1)])
+def test_oracle_parity_three_chunks(dim, distance):
+    """257 <= dim <= 384: rows of three 128-element chunks run the four-chunk
+    kernels, whose L1 sign words (two a chunk) set the stride of the per-update
+    sign buffer; with the three-chunk stride an update's last words landed on the
+    next update's first.  The tiny set, two epochs; L2 (no sign words) alongside."""
+    _oracle_vs_engine(tiny(), dim, 2, distance=distance, batches=10)
+
+
 def test_single_batch_and_duplicates():
     """batches=1 (one batch = the whole set) and duplicated / self-loop triples."""
     ds = data.synthetic("tiny", seed=5)

@@ -83,7 +83,9 @@ def test_oracle_parity_with_transrnorm(compat, dim, shape):
 
 
 def test_fp32_statistically_close():
-    """See test_gpu_transh.test_fp32_statistically_close for why FP32 is statistical."""
+    """See test_gpu_transh.test_fp32_statistically_close for why FP32 is statistical
+    over an epoch; test_gpu_fp32_step.py holds the float owner kernels to the
+    oracle element by element, one batch at a time."""
     ds = data.synthetic("small", seed=6)
     kw = dict(rate=0.005, batches=25, transr_compat=False)
     m = oracle_model("R", ds, 32, **kw)
@@ -156,8 +158,10 @@ def test_fp32_wide_statistically_close():
     the margin and transRNorm amplifies the flips, so the drift from the FP64
     oracle grows with the dim (diagnostic tools/diag/fp32_wide_probe.py: median
     entity drift 5.5e-3 at 120, 7.7e-3 at 190, 9.4e-3 at 200 after one epoch) and
-    the bar is statistical: loss and active count within 1 %, and the L2 form's
-    drift no larger than the LDS form's next to it (2x), not an absolute ulp bound."""
+    the bar over an epoch is statistical: loss and active count within 1 %, and the
+    L2 form's drift no larger than the LDS form's next to it (2x), not an absolute
+    ulp bound.  The element-wise bound on the same widths is per batch:
+    test_gpu_fp32_step.py (n = 190, 200, 512)."""
     d190 = _fp32_vs_oracle("small", 190)
     d200 = _fp32_vs_oracle("small", 200)
     d512 = _fp32_vs_oracle("tiny", 512)
