@@ -1803,6 +1803,13 @@ kb2e_status kb2e_take_stats(kb2e_ctx* c, double* loss, int64_t* active) {
                 for (int k = 8; k < 24; ++k) fprintf(stderr, " %llu", q[k]);
                 fprintf(stderr, "; hot relations (%llu, %llu chunks, %llu violators):", q[41], q[40], q[42]);
                 for (int k = 24; k < 40; ++k) fprintf(stderr, " %llu", q[k]);
+                if (c->rpar_cons_seq) {  // the pipelined kernel's stamps after the chunk loop
+                    fprintf(stderr, "; tail (last debt + barrier, slices to LDS + barrier, records, W write-back):");
+                    for (int k = 44; k < 48; ++k) fprintf(stderr, " %llu", q[k]);
+                    fprintf(stderr, "; hot tail:");
+                    for (int k = 48; k < 52; ++k) fprintf(stderr, " %llu", q[k]);
+                    fprintf(stderr, "; hot cycles %llu", q[43]);
+                }
                 fprintf(stderr, "\n");
             }
             if (c->rpar_cons_wave)

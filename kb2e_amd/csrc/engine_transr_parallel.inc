@@ -331,6 +331,13 @@ void build_transr_tiles(kb2e_ctx* c, bool tiles, hipStream_t st, int set) {
 // buffer set 0 or 1 of a double-buffered export (sub-batches)
 DevBuf& buf_set(int set, DevBuf& s0, DevBuf& s1) { return set ? s1 : s0; }
 
+// sub-batches: phase A on its own stream beside phase B (KB2E_SUB_OVERLAP=0: everything
+// in line on the batch stream, A/B and tests; read at every batch)
+bool sub_overlap_on() {
+    const char* e = getenv("KB2E_SUB_OVERLAP");
+    return !(e && e[0] == '0');
+}
+
 // One index batch: sub-batch j of batch b (the whole batch when c->sub == 1).  Phase
 // A (energies, hinge, directions, the matrix partials) reads the tables bfa names
 // -- the start-of-batch copies when the batch runs in sub-batches -- and phase B
@@ -342,8 +349,7 @@ void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
     // in buffer set j & 1 (the set phase B of sub-batch j - 2 no longer reads); phase A
     // of sub-batch 0 in line on the batch stream (a wait across queues costs ~12 us:
     // r23 timeline)
-    static const bool ov_on = !(getenv("KB2E_SUB_OVERLAP") && getenv("KB2E_SUB_OVERLAP")[0] == '0');  // (A/B)
-    const bool ov = c->sub > 1 && ov_on;
+    const bool ov = c->sub > 1 && sub_overlap_on();
     const bool side = ov && j > 0;
     const int set = ov ? (j & 1) : 0;
     hipStream_t sa = side ? c->suba_stream : c->stream;
@@ -424,6 +430,7 @@ void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
         if (const char* dbg = getenv("KB2E_CONS_DBG")) bf.dbg = atoi(dbg);  // timing experiments only
         if (const char* cl = getenv("KB2E_RPAR_CHAIN_LIST")) bf.chain_list = std::max(64, atoi(cl));  // tests
         if (const char* ct = getenv("KB2E_RPAR_CHAIN_TILES")) bf.chain_tiles = std::max(1, atoi(ct));  // tests
+        if (const char* rc = getenv("KB2E_RPAR_REC_CAP")) bf.rec_cap = std::max(4, atoi(rc));  // tests
     }
     if (c->rpar_cons_wide || c->rpar_cons_gen || c->rpar_widep) {  // the chains past n = 64: pair flags, pre / post split
         bf.pflag = buf_set(set, c->rpar_pflag, c->sb_pflag).as<uint8_t>();
@@ -608,6 +615,8 @@ void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
 template <typename T>
 void run_batch_transr_parallel(kb2e_ctx* c, int64_t b) {
     if (c->sub > 1) {  // the start-of-batch tables for every sub-batch's phase A
+        // (made on the side stream beside phase A of sub-batch 0, which then read the live
+        // tables, they gained nothing: DESIGN.md section 7 round 8)
         for (auto pr : {std::make_pair(&c->snap_ent, &c->ent), std::make_pair(&c->snap_rel, &c->rel),
                         std::make_pair(&c->snap_w, &c->w)})
             HIPCHK(hipMemcpyAsync(pr.first->p, pr.second->p, pr.second->bytes, hipMemcpyDeviceToDevice, c->stream));

@@ -221,6 +221,7 @@ struct RParBufs {
     int32_t dbg;         // transRNorm wave kernel: phases skipped for timing experiments (tools; wrong results)
     int32_t chain_list;  // pipelined chain kernel: pairs a window (0: all that fit the LDS; tests force windows)
     int32_t chain_tiles; // chain kernels: tiles a window (0: the prefix table's 256; tests force windows)
+    int32_t rec_cap;     // pipelined chain kernel: records a stage-full of its record pass (0: all that fit the LDS; tests)
     int32_t* vio;        // n <= 64 chain kernels: [tiles][kCPairs] the violators' slots of the relation whose
                          // first tile it is (-2: (entity[r], r)); its pair records are made in-kernel
     uint32_t* err;       // pipelined chain: a bounded in-workgroup wait timed out (the host fails loudly)

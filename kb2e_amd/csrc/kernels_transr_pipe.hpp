@@ -58,6 +58,116 @@ __host__ __device__ constexpr size_t pipe_lds(int n) {
            sizeof(int) * (size_t)(2 * kPipeList + kSeqMaxTiles + 1 + 8 + 2 * kChainRows);
 }
 
+constexpr int kRecGroup = 32;  // G rows a wave has in flight from global memory (pipe_records: one round of
+                               // loads for the hottest relation's ~25 records a wave)
+constexpr int kRecReads = 8;   // 16-byte LDS reads of a staged G row a group (two groups in flight)
+
+// The relation's pair records G -> da = -lr W G with its final matrix
+// (transr/trainer.cpp:59-60; first order in lr the same as the matrix at the
+// pair's chunk), at the end of its chain: the nvt violator slots in vio (written
+// during the chain), W_c in LDS (stride L).  (Made here, the records of the ~440
+// relations that finish early overlap the hottest relation's chain instead of
+// following it in a kernel of their own.)  W_c's row is the same for every record of
+// the relation: lane j takes row j of the final W_c into registers once (the
+// walker's K0 column and the helpers' W_c fragments are dead by now), and a wave
+// stages its records' G rows a stage-full at a time -- kRecGroup global loads in
+// flight a lane, then LDS -- in the A slots and P buffers the walk left (`stage`,
+// STAGE elements: a quarter a wave; `slots`: the wave's record slots, the window
+// lists' space).  A record is then NP / 2 16-byte LDS reads that every lane makes at
+// the same address (no bank conflicts) and NP FMAs: the four chains by i mod 4 over
+// i = 0 .. NP - 1, (acc0 + acc1) + (acc2 + acc3), then -lr da (no other order: the
+// records are compared bit for bit across changes of this pass).  Wave
+// w takes records w, w + 4, ...; nothing here needs a workgroup barrier.  The first
+// nslist violator slots are also in LDS (slist, written beside vio during the chain),
+// which saves the hottest relation a round trip to global memory.  bf.rec_cap
+// (tests): fewer records a stage-full, so small relations take several.
+template <typename T, int NP, int L, int STAGE>
+__device__ __forceinline__ void pipe_records(const RParArgs& a, const RParBufs<T>& bf, int r, const int32_t* vio,
+                                             int nvt, const T* Wc, T* stage, int* slots, const int* slist,
+                                             int nslist) {
+    typedef T T2 __attribute__((ext_vector_type(2)));
+    constexpr int NW = kChainThreads / kWave;
+    constexpr int CAPW = STAGE / (NW * NP);  // records a wave stages at a time
+    static_assert(CAPW >= 1 && NW * CAPW <= kPipeList, "the record slots borrow a window list");
+    static_assert(NP % 4 == 0 && (L * sizeof(T)) % 16 == 0 && (NP * sizeof(T)) % 16 == 0, "16-byte LDS reads");
+    const int n = a.n, ld = a.ld, w = threadIdx.x >> 6, l = lane_id();
+    const int nmine = nvt > w ? (nvt - w + NW - 1) / NW : 0;  // records w, w + NW, ...
+    if (nmine == 0) return;
+    const int capw = bf.rec_cap >= NW && bf.rec_cap < NW * CAPW ? bf.rec_cap / NW : CAPW;
+    T* gs = stage + w * (CAPW * NP);
+    int* sl = slots + w * CAPW;
+    auto row_of = [&](int s) { return s >= 0 ? bf.pair + (int64_t)s * ld : bf.relpair + (int64_t)r * ld; };
+    T wr[NP];  // row j of the final matrix
+    {
+        const T2* w2 = (const T2*)(Wc + (l < NP ? l : 0) * L);
+#pragma unroll
+        for (int q = 0; q < NP / 2; ++q) {
+            const T2 x = w2[q];
+            wr[2 * q] = x.x;
+            wr[2 * q + 1] = x.y;
+        }
+    }
+    for (int m0 = 0; m0 < nmine; m0 += capw) {
+        const int cnt = nmine - m0 < capw ? nmine - m0 : capw;
+        for (int i = l; i < cnt; i += kWave) {
+            const int k = w + NW * (m0 + i);
+            sl[i] = k < nslist ? slist[k] : vio[k];
+        }
+        wave_lds_sync();
+        for (int i0 = 0; i0 < cnt; i0 += kRecGroup) {
+            // the group's slots as wave-uniform values (one LDS read; past the end the last
+            // record's again, so the loads and the LDS stores need no branches)
+            const int iu = i0 + (l & (kRecGroup - 1));
+            const int sv = sl[iu < cnt ? iu : cnt - 1];
+            T g[kRecGroup];
+#pragma unroll
+            for (int u = 0; u < kRecGroup; ++u) g[u] = row_of(__builtin_amdgcn_readlane(sv, u))[l < n ? l : 0];
+            if (l < NP) {
+#pragma unroll
+                for (int u = 0; u < kRecGroup; ++u)
+                    gs[(i0 + u < cnt ? i0 + u : cnt - 1) * NP + l] = l < n ? g[u] : T(0);
+            }
+        }
+        wave_lds_sync();
+        // A record's staged row in groups of kRecReads reads, LA groups in flight across
+        // the records (the next record's first groups are read under this one's last
+        // FMAs; after the last record the same row again), so the LDS, which the four
+        // waves share, stays busy: all NP / 2 reads of a record at once would take the
+        // registers that hold W_c's row and leave the LDS idle during the FMAs.
+        constexpr int NG = (NP / 2 + kRecReads - 1) / kRecReads, LA = NG >= 2 ? 2 : 1;
+        T2 gr[NP / 2];
+        auto g_load = [&](int i, int gq) {
+            const T2* g2 = (const T2*)(gs + i * NP);
+#pragma unroll
+            for (int q = gq * kRecReads; q < (gq + 1) * kRecReads && q < NP / 2; ++q) gr[q] = g2[q];
+        };
+#pragma unroll
+        for (int gq = 0; gq < LA; ++gq) g_load(0, gq);
+        for (int i = 0; i < cnt; ++i) {
+            T* row = row_of(sl[i]);
+            const int inext = i + 1 < cnt ? i + 1 : i;
+            T acc[4] = {T(0), T(0), T(0), T(0)};
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int gq = 0; gq < NG; ++gq) {
+#pragma unroll
+                for (int q = gq * kRecReads; q < (gq + 1) * kRecReads && q < NP / 2; ++q) {
+                    acc[(2 * q) & 3] = fma(wr[2 * q], gr[q].x, acc[(2 * q) & 3]);
+                    acc[(2 * q + 1) & 3] = fma(wr[2 * q + 1], gr[q].y, acc[(2 * q + 1) & 3]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                if (gq + LA < NG) g_load(i, gq + LA);
+                else g_load(inext, gq + LA - NG);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            T da = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+            asm volatile("" : "+v"(da));  // (keeps the FMAs out of the store's lane branch, between the reads)
+            if (l < n) row[l] = -(T)a.lr * da;
+        }
+        wave_lds_sync();  // (every lane has read the staged rows before the next stage-full lands)
+    }
+}
+
 // STATS: the KB2E_RPAR_STATS instantiation (cycle stamps of the phases, violator and
 // round counts); the product kernel carries none of it
 template <typename T, int KS, bool STATS>
@@ -84,7 +194,9 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     T* Abuf = Wc + NP * L;      // [3][R][L] entity rows of chunks k, k+1, k+2
     T* Pbuf = Abuf + 3 * R * L;  // [2][R][L] projections (then the violators' G rows) of chunks k, k+1
     T* Gbuf = Pbuf + 2 * R * L;  // [2][R][LG] Gram matrices A A^T of chunks k, k+1
-    T* Cx = Gbuf + 2 * R * LG;   // [R][LG] A_{k+1} A_k^T
+    T* Cx = Gbuf + 2 * R * LG;   // [R][LG] A_{k+1} A_k^T (correct_q; unused since the dots are made on the fly)
+    int* slist = (int*)Cx;       // ... so it holds the relation's first kSlist violator slots for pipe_records
+    constexpr int kSlist = 2 * R * LG;
     T* qpart = Cx + R * LG;      // [4][R] |p_j|^2 partials of the column slices (next chunk)
     T* rp = qpart + 4 * R;       // [4][NP] row partials of the tail renorm
     int* pe = (int*)(rp + 4 * NP);
@@ -95,14 +207,16 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     const long long ck0 = STATS ? clock64() : 0;
     int n_chunks = 0;
     unsigned long long n_vio = 0, n_rounds = 0, max_m = 0;
-    __shared__ unsigned long long ph[STATS ? 16 : 1];  // (LDS, not sixteen 64-bit registers)
-    if (STATS && threadIdx.x < 16) ph[threadIdx.x] = 0;
+    __shared__ unsigned long long ph[STATS ? 20 : 1];  // (LDS, not twenty 64-bit registers)
+    if (STATS && threadIdx.x < 20) ph[threadIdx.x] = 0;
     long long tq = ck0;
     // (phases 12..15 on thread 64, helper wave 1: debt, tiles, helper_sync wait, rows +
-    // corrections incl. the wait for the walk's end)
+    // corrections incl. the wait for the walk's end; 16..19 on thread 0, what follows the
+    // chunk loop: a window's last debt + barrier, the helpers' slices to LDS + barrier,
+    // the records, the W write-back)
     auto tick = [&](int k) {
         if constexpr (STATS) {
-            if (threadIdx.x == (k >= 12 || k == 5 ? 64u : 0u)) {
+            if (threadIdx.x == ((k >= 12 && k < 16) || k == 5 ? 64u : 0u)) {
                 const long long t = clock64();
                 ph[k] += (unsigned long long)(t - tq);
                 tq = t;
@@ -292,7 +406,7 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     // row (one DPP row), NP / 16 columns each, rows rs, rs + 12, rs + 24.  The same
     // FMAs per element in the same order as correct_q.
     // The chunk's outputs to global memory are made here too, off the walker: each
-    // violator's pair record G (da = -lr W G with the final matrix: chain_records) and
+    // violator's pair record G (da = -lr W G with the final matrix: pipe_records) and
     // vio slot as it is published (the sixteen threads of row group 0 hold the G row),
     // and after the walk the chunk's pair flags from the walker's mask (misc[1 + 2 vpar],
     // written before misc[6]); (entity'[r], r) marks the relation.  cn = 0 (the
@@ -347,7 +461,10 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
 #pragma unroll
                     for (int u = 0; u < NE; ++u)
                         if (cb + u < n) dst[cb + u] = gv[u];
-                    if (ht == 0) vio[nvt + used] = slv;
+                    if (ht == 0) {
+                        vio[nvt + used] = slv;
+                        if (nvt + used < kSlist) slist[nvt + used] = slv;
+                    }
                 }
             }
             if (done) {
@@ -818,10 +935,11 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
         apply_pending();
         pend_nv = 0;
         __syncthreads();
+        tick(16);
         gw += ntile;
         if (last || gw >= g0 + run) break;
     }
-    // the relation's matrix back: the helpers' slices into LDS (the records' matrix), then HBM
+    // the helpers' slices into LDS: the relation's final matrix, for the records and HBM
     if (w > 0) {
 #pragma unroll
         for (int si = 0; si < NSW; ++si) {
@@ -833,10 +951,33 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
         }
     }
     __syncthreads();
-    if (mine && col < n)
-        for (int jj = 0; jj < n; ++jj) bf.W[((int64_t)r * n + jj) * ld + col] = Wc[jj * L + col];
-    chain_records<T, NP, L>(a, bf, r, vio, nvt, Wc, Pbuf, 2 * R * L);
+    tick(17);
+    // the records first (the A slots, the P buffers and the window lists are free), so
+    // that their G row loads queue behind no store; then the matrix to HBM, whole rows
+    // by all threads
+    pipe_records<T, NP, L, 5 * R * L>(a, bf, r, vio, nvt, Wc, Abuf, pe, slist, kSlist);
     if constexpr (STATS) {
+        __syncthreads();  // (the slowest wave's records)
+        tick(18);
+    }
+    {
+        constexpr int NWB = NP * NP / kChainThreads;  // (every LDS read in flight before the first store)
+        static_assert(NWB * kChainThreads == NP * NP, "whole rounds of the write-back");
+        T wv[NWB];
+#pragma unroll
+        for (int q = 0; q < NWB; ++q) {
+            const int idx = threadIdx.x + q * kChainThreads;
+            wv[q] = Wc[(idx / NP) * L + idx % NP];
+        }
+#pragma unroll
+        for (int q = 0; q < NWB; ++q) {
+            const int idx = threadIdx.x + q * kChainThreads;
+            const int jj = idx / NP, i = idx % NP;
+            if (jj < n && i < n) bf.W[((int64_t)r * n + jj) * ld + i] = wv[q];
+        }
+    }
+    if constexpr (STATS) {
+        tick(19);
         if (threadIdx.x == 0) {
             const unsigned long long cyc = (unsigned long long)(clock64() - ck0);
             atomicAdd(&g_seq_stats[0], 1ull);
@@ -848,11 +989,14 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
             atomicMax(&g_seq_stats[6], (unsigned long long)n_chunks);
             atomicMax(&g_seq_stats[7], max_m);
             for (int k = 0; k < 16; ++k) atomicAdd(&g_seq_stats[8 + k], ph[k]);
+            for (int k = 0; k < 4; ++k) atomicAdd(&g_seq_stats[44 + k], ph[16 + k]);
             if (n_chunks >= 12) {  // (the hottest relation of a default half-batch walks 15-18 chunks)
                 for (int k = 0; k < 16; ++k) atomicAdd(&g_seq_stats[24 + k], ph[k]);
                 atomicAdd(&g_seq_stats[40], (unsigned long long)n_chunks);
                 atomicAdd(&g_seq_stats[41], 1ull);
                 atomicAdd(&g_seq_stats[42], n_vio);
+                atomicAdd(&g_seq_stats[43], cyc);
+                for (int k = 0; k < 4; ++k) atomicAdd(&g_seq_stats[48 + k], ph[16 + k]);
             }
         }
     }

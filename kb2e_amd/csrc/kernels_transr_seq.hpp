@@ -31,7 +31,7 @@
 // own last update (bf.last_renorm, kernels_transr_parallel.hpp).
 //
 // This file holds the semantics above and what the chain kernels share (the
-// rounds, wave sums, the block -> relation map, the pair records); the kernels
+// rounds, wave sums, the block -> relation map); the kernels
 // are kernels_transr_pipe.hpp (n <= 64), kernels_transr_chainwp.hpp (64 < n <=
 // 100), kernels_transr_chainw.hpp (the lockstep form) and kernels_transr_chaing.hpp
 // (FP32 and the other widths).
@@ -48,7 +48,9 @@ constexpr int kSeqMaxTiles = 256;   // tiles of one relation a window (the prefi
 // KB2E_RPAR_STATS: 0 relations, 1 chunks, 2 violators, 3 rounds, 4 cycles sum, 5 max, 6 most chunks, 7 most rounds,
 // 8..23 cycles of the phases (thread 0: prologue, load issue, S1 MFMA issue, S1 sums, B1, mask + K0, S3 MFMA
 // issue, S3 sums, rows + B2, rounds, shuffles, S5, S6), 24..39 the same over relations of >= 40 chunks,
-// 40 their chunks, 41 their count
+// 40 their chunks, 41 their count, 42 their violators; the pipelined kernel (kernels_transr_pipe.hpp, hot: >= 12
+// chunks) also 43 the hot relations' cycles sum, 44..47 what follows the chunk loop (a window's last debt + barrier,
+// the helpers' slices to LDS + barrier, the records, the W write-back), 48..51 the same over the hot relations
 static __device__ unsigned long long g_seq_stats[64];
 
 // sums over the 16 lanes of a DPP row (lanes l & ~15 ... l | 15), in every lane of
@@ -175,62 +177,5 @@ __device__ __forceinline__ bool chain_first_tile(const RParArgs& a, int t0, int 
     g0 = lo - t0;
     return true;
 }
-
-// The relation's pair records G -> da = -lr W G with its final matrix
-// (transr/trainer.cpp:59-60; first order in lr the same as the matrix at the
-// pair's chunk), at the end of its chain: the nvt violator slots in vio (written
-// during the chain), W_c in LDS (stride L), `stage` (stage_cap doubles) free LDS: [4][L] rows, then the slot list.  A wave a
-// record: the G row staged in LDS, lane j makes da_j = sum_i W[j][i] G_i (four
-// chains).  (Made here, the records of the ~440 relations that finish early
-// overlap the hottest relation's chain instead of following it in a kernel of
-// their own.)
-template <typename T, int NP, int L>
-__device__ __forceinline__ void chain_records(const RParArgs& a, const RParBufs<T>& bf, int r, const int32_t* vio,
-                                              int nvt, const T* Wc, T* stage, int stage_cap) {
-    const int n = a.n, ld = a.ld, w = threadIdx.x >> 6, l = lane_id();
-    const int nw = blockDim.x >> 6;
-    T* gs = stage + w * L;
-    // the violator slots in LDS when they fit (after the waves' staged rows), so a
-    // record's G row load waits on no global slot load; the rows prefetched PF
-    // records ahead (a hot relation has ~150 records a batch: ~40 a wave)
-    int* sl_l = (int*)(stage + nw * L);
-    const bool lds_sl = nvt <= 2 * (stage_cap - nw * L);
-    if (lds_sl) {
-        for (int i = threadIdx.x; i < nvt; i += blockDim.x) sl_l[i] = vio[i];
-        __syncthreads();
-    }
-    auto row_of = [&](int k) {
-        const int sl = lds_sl ? sl_l[k] : vio[k];
-        return sl >= 0 ? bf.pair + (int64_t)sl * ld : bf.relpair + (int64_t)r * ld;
-    };
-    constexpr int PF = 4;
-    T pre[PF];
-#pragma unroll
-    for (int p = 0; p < PF; ++p) {
-        const int k = w + p * nw;
-        pre[p] = k < nvt && l < n ? row_of(k)[l] : T(0);
-    }
-    for (int k = w; k < nvt; k += nw) {
-        T* row = row_of(k);
-        if (l < NP) gs[l] = pre[0];
-#pragma unroll
-        for (int p = 0; p + 1 < PF; ++p) pre[p] = pre[p + 1];
-        {
-            const int kn = k + PF * nw;
-            pre[PF - 1] = kn < nvt && l < n ? row_of(kn)[l] : T(0);
-        }
-        wave_lds_sync();
-        T acc[4] = {T(0), T(0), T(0), T(0)};
-        const int j = l < NP ? l : 0;
-#pragma unroll
-        for (int i = 0; i < NP; i += 4)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[u] = fma(Wc[j * L + i + u], gs[i + u], acc[u]);
-        const T da = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-        wave_lds_sync();  // (every lane has read the staged row before the next one lands)
-        if (l < n) row[l] = -(T)a.lr * da;
-    }
-}
-
 
 }  // namespace kb2e

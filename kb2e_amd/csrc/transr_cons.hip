@@ -110,7 +110,7 @@ void cons_seq_launch(const RParArgs& a, const RParBufs<double>& bf, size_t lds, 
     RParBufs<double> bb = bf;
     void* args[] = {&aa, &bb};
     // one workgroup per relation of the batch, most frequent first (chain_first_tile);
-    // the pair records are made at the end of each relation's chain (chain_records)
+    // the pair records are made at the end of each relation's chain (pipe_records)
     HIPCHK(hipLaunchKernel(pipe_fn(a.n, bf.stats != 0), dim3(chain_grid(a)), dim3(kChainThreads), args, lds, stream));
 }
 

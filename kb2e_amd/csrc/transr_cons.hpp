@@ -30,7 +30,7 @@ void grad_wave_launch(const RParArgs& a, const RParBufs<T>& bf, int grid, hipStr
 // transRNorm per relation, pair by pair, in chunks of 32 (kernels_transr_pipe.hpp; FP64,
 // n <= 64): dynamic LDS bytes (and the kernel's limit raised to it); the launch, one
 // workgroup per relation of the batch (a.brel, most frequent first), each making its
-// relation's pair records at the end of its chain (chain_records).
+// relation's pair records at the end of its chain (pipe_records).
 size_t cons_seq_setup(int n);
 void cons_seq_launch(const RParArgs& a, const RParBufs<double>& bf, size_t lds, hipStream_t stream);
 // transRNorm per relation, pair by pair, for n <= 112 (kernels_transr_chainw.hpp,
