@@ -198,6 +198,14 @@ struct kb2e_ctx {
     DevBuf rpar_y, rpar_wpart, rpar_rpart, rpar_tile_act, rpar_pair, rpar_relpair, rpar_relpair_stamp, rpar_scan_pre, rpar_tiles,
         rpar_ntiles, rpar_tile_first, rpar_rel_begin, rpar_scan;
     DevBuf rpar_ptab;  // transRNorm pair dedupe: three (relation, entity) tables in rotation
+                       // (merged phase A: two groups of `sub` tables)
+    // n <= 64 wave path with sub-batches: phase A of all of a batch's sub-batches in one
+    // set of launches on the batch stream, before its first phase B -- no start-of-batch
+    // copies, no side stream (KB2E_RPAR_MERGE_A=0: phase A per sub-batch); its geometry;
+    // batches run so far (the pair-table group)
+    bool rpar_merge_a = false;
+    RParMerge rpar_merge{};
+    uint32_t rpar_merge_batches = 0;
     DevBuf rpar_batch_t0, rpar_td_r, rpar_td_cnt, rpar_td_kk, rpar_td_ent;  // per-epoch tile descriptors
     DevBuf sh_rpar_batch_t0, sh_rpar_td_r, sh_rpar_td_cnt, sh_rpar_td_kk, sh_rpar_td_ent;
     // per batch: the relations it holds, most frequent first (the chain kernels' blocks), and

@@ -114,8 +114,33 @@ void setup_transr_parallel(kb2e_ctx* c) {
     // matrix partials: one per tile (gradient step), one per (tile, row block) for
     // the register-resident transRNorm kernel
     const bool cw = cons_wave_supported(c->n) && mst > 0;
-    c->rpar_wpart.alloc((size_t)c->rpar_max_tiles * (cw ? kConsPpt : 1) * c->n * c->ld * es);
-    c->rpar_rpart.alloc((size_t)c->rpar_max_tiles * c->ld * es);
+    // sub-batches on the n <= 64 wave path (the condition of rpar_cons_wave below): phase
+    // A once a batch for all of them (KB2E_RPAR_MERGE_A=0: per sub-batch, on the
+    // start-of-batch copies), unless the compat scan of a sub-batch takes the chunk
+    // prefix kernel (more than kScanDirectMax chunks, or KB2E_RPAR_SCAN_PREFIX=1)
+    c->rpar_merge_a = false;
+    c->rpar_merge = RParMerge{};
+    if (c->sub > 1 && c->rpar_mfma && cw && c->rpar_St <= 8 && !(ck0 && std::string(ck0) == "tile")) {
+        const char* ma = getenv("KB2E_RPAR_MERGE_A");
+        const char* sp = getenv("KB2E_RPAR_SCAN_PREFIX");
+        const int64_t nch = (2 * c->Bs + kScanChunk - 1) / kScanChunk;
+        const bool use_pre = g.transr_compat && (sp ? sp[0] == '1' : nch > kScanDirectMax);
+        c->rpar_merge_a = !(ma && ma[0] == '0') && !use_pre;
+    }
+    // tile slots: of a batch, or (merged phase A) `sub` times a sub-batch's, side by side
+    int64_t tslots = c->rpar_max_tiles;
+    if (c->rpar_merge_a) {
+        RParMerge& m = c->rpar_merge;
+        m.sub = c->sub;
+        m.Bs = (int32_t)c->Bs;
+        m.Blast = (int32_t)(c->B - (int64_t)(c->sub - 1) * c->Bs);
+        m.tcap = (int32_t)(std::min<int64_t>(g.num_relations, c->Bs) + c->Bs / c->rpar_St + 1);
+        m.nch = (int32_t)((2 * c->Bs + kScanChunk - 1) / kScanChunk);
+        m.brel_cap = (int32_t)std::min<int64_t>(g.num_relations, c->Bs);
+        tslots = (int64_t)m.sub * m.tcap;
+    }
+    c->rpar_wpart.alloc((size_t)tslots * (cw ? kConsPpt : 1) * c->n * c->ld * es);
+    c->rpar_rpart.alloc((size_t)tslots * c->ld * es);
     c->rpar_tile_act.alloc((size_t)(nkeys + 1) * 4);
     c->rpar_pair.alloc((size_t)c->B * 4 * c->ld * es);
     c->rpar_relpair.alloc((size_t)g.num_relations * c->ld * es);
@@ -136,7 +161,7 @@ void setup_transr_parallel(kb2e_ctx* c) {
     }
     if (c->rpar_widep) c->rpar_wsc.alloc((size_t)c->rpar_brel_cap * c->n * c->ld * 8);
     else c->rpar_wsc.free();
-    if (c->sub > 1) {  // the start-of-batch tables phase A reads while phase B runs sub-batch by sub-batch
+    if (c->sub > 1 && !c->rpar_merge_a) {  // the start-of-batch tables phase A reads while phase B runs sub-batch by sub-batch
         c->snap_ent.alloc(c->ent.bytes);
         c->snap_rel.alloc(c->rel.bytes);
         c->snap_w.alloc(c->w.bytes);
@@ -155,22 +180,28 @@ void setup_transr_parallel(kb2e_ctx* c) {
         c->B * 4 >= (1 << kPtabSlotBits))
         throw std::invalid_argument("PARALLEL TransR: at most 2^24 - 2 entities, 2^18 - 2 relations, 2^20 - 1 samples a batch");
     {  // the pair-dedupe tables: >= 3x the batch's update slots, a power of two, all empty;
-       // three of them in rotation (sub-batches: phase A runs one sub-batch ahead)
+       // three of them in rotation (sub-batches: phase A runs one sub-batch ahead), or
+       // (merged phase A) two groups of `sub`, each for a sub-batch's slots
         size_t sz = 1024;
-        while (sz < (size_t)c->B * 4 * 3) sz <<= 1;
+        while (sz < (size_t)(c->rpar_merge_a ? c->Bs : c->B) * 4 * 3) sz <<= 1;
+        const size_t ntab = c->rpar_merge_a ? 2 * (size_t)c->sub : 3;
         c->rpar_ptab_mask = (uint32_t)(sz - 1);
-        c->rpar_ptab.alloc(3 * sz * 8);
-        memset_sync(c->rpar_ptab.p, 0xff, 3 * sz * 8);
+        c->rpar_ptab.alloc(ntab * sz * 8);
+        memset_sync(c->rpar_ptab.p, 0xff, ntab * sz * 8);
+        c->rpar_merge_batches = 0;
     }
     const int scan_chunk = c->rpar_widep ? c->rpar_wg.chunk : kScanChunk;
-    c->rpar_scan.alloc((size_t)((2 * c->B + scan_chunk - 1) / scan_chunk) * 2 * c->n * 8);
+    // (merged phase A: every sub-batch its own chunking, m.nch chunk slots each)
+    c->rpar_scan.alloc((size_t)std::max<int64_t>((2 * c->B + scan_chunk - 1) / scan_chunk,
+                                                  (int64_t)c->rpar_merge.sub * c->rpar_merge.nch) *
+                       2 * c->n * 8);
     c->rpar_scan_pre.alloc(c->rpar_scan.bytes);
     c->rpar_pflag.alloc((size_t)c->B * 4);
-    c->rpar_cons_tile.alloc((size_t)c->rpar_max_tiles * (cw ? kConsPpt : 1) * 4);
+    c->rpar_cons_tile.alloc((size_t)tslots * (cw ? kConsPpt : 1) * 4);
     if (cw) {  // register-fragment kernels: compacted transRNorm pairs
-        c->rpar_cpairs.alloc((size_t)c->rpar_max_tiles * 2 * kCPairs * 4);
-        c->rpar_vio.alloc((size_t)c->rpar_max_tiles * kCPairs * 4);
-        c->rpar_cnrows.alloc((size_t)c->rpar_max_tiles * 4);
+        c->rpar_cpairs.alloc((size_t)tslots * 2 * kCPairs * 4);
+        c->rpar_vio.alloc((size_t)tslots * kCPairs * 4);
+        c->rpar_cnrows.alloc((size_t)tslots * 4);
     }
     size_t tb = 0;
     HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (int32_t*)nullptr, (int32_t*)nullptr, (int)(nkeys + 1),
@@ -208,6 +239,7 @@ void setup_transr_parallel(kb2e_ctx* c) {
         const char* ck = getenv("KB2E_RPAR_CONS");
         // (the wave kernels take St <= 8: choose_mfma_samples never exceeds it)
         c->rpar_cons_wave = cw && c->rpar_St <= 8 && !(ck && std::string(ck) == "tile");
+        if (c->rpar_merge_a && !c->rpar_cons_wave) throw std::logic_error("merged phase A off the wave path");
         if (c->rpar_cons_wave) c->rpar_cons_lds = cons_wave_setup(c->n, c->rpar_St, c->esize);
         // FP64: the relation's pairs one after another, each against the matrix the
         // earlier ones left (default on the wave path; KB2E_RPAR_CONS=jacobi: every pair
@@ -251,7 +283,8 @@ void setup_transr_parallel(kb2e_ctx* c) {
     } else {
         for (DevBuf* d : {&c->rpar_batch_t0, &c->rpar_td_r, &c->rpar_td_cnt, &c->rpar_td_kk, &c->rpar_td_ent}) d->free();
     }
-    // sub-batches: phase A's second export set (the same sizes)
+    // sub-batches: phase A's second export set (the same sizes; merged phase A: none,
+    // its sub-batches' exports lie side by side in the first set)
     {
         const std::pair<DevBuf*, DevBuf*> sets[] = {
             {&c->sb_x, &c->xreal}, {&c->sb_d, &c->aux}, {&c->sb_y, &c->rpar_y}, {&c->sb_wpart, &c->rpar_wpart},
@@ -259,13 +292,15 @@ void setup_transr_parallel(kb2e_ctx* c) {
             {&c->sb_cpairs, &c->rpar_cpairs}, {&c->sb_vio, &c->rpar_vio}, {&c->sb_cnrows, &c->rpar_cnrows}};
         for (const auto& pr : sets) {
             pr.first->free();
-            if (c->sub > 1 && pr.second->p) {
+            if (c->sub > 1 && !c->rpar_merge_a && pr.second->p) {
                 pr.first->alloc(pr.second->bytes);
                 memset_sync(pr.first->p, 0, pr.first->bytes);
             }
         }
     }
-    for (const void* k : {(const void*)rpar_scan_energy_kernel<double>, (const void*)rpar_scan_energy_kernel<float>})
+    for (const void* k : {(const void*)rpar_scan_energy_kernel<double>, (const void*)rpar_scan_energy_kernel<float>,
+                          (const void*)rpar_scan_energy_merged_kernel<double>,
+                          (const void*)rpar_scan_energy_merged_kernel<float>})
         (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rpar_scan_lds(c));
     // a refused limit above (an image no launch of this context uses) must not linger
     // as the sticky last error for the next launch check
@@ -338,25 +373,14 @@ bool sub_overlap_on() {
     return !(e && e[0] == '0');
 }
 
-// One index batch: sub-batch j of batch b (the whole batch when c->sub == 1).  Phase
-// A (energies, hinge, directions, the matrix partials) reads the tables bfa names
-// -- the start-of-batch copies when the batch runs in sub-batches -- and phase B
-// applies the sub-batch's sums, norms and transRNorm pairs to the live tables.
+// The kernel arguments of sub-batch j of batch b (the whole batch when c->sub == 1), its
+// exports in buffer set `set`; all but the pair-dedupe tables and the stamp.
 template <typename T>
-void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
-    // sub-batches: phase A of sub-batch j >= 1 on its own stream (it reads the
-    // start-of-batch copies, so it runs beside phase B of sub-batch j - 1), its exports
-    // in buffer set j & 1 (the set phase B of sub-batch j - 2 no longer reads); phase A
-    // of sub-batch 0 in line on the batch stream (a wait across queues costs ~12 us:
-    // r23 timeline)
-    const bool ov = c->sub > 1 && sub_overlap_on();
-    const bool side = ov && j > 0;
-    const int set = ov ? (j & 1) : 0;
-    hipStream_t sa = side ? c->suba_stream : c->stream;
+void fill_rpar(kb2e_ctx* c, int64_t b, int j, int set, RParArgs& a, RParBufs<T>& bf) {
     const int64_t ib = b * c->sub + j;                   // index batch
     const int64_t first = b * c->B + (int64_t)j * c->Bs;  // its first sample
     const int64_t cnt = std::min<int64_t>(c->Bs, c->B - (int64_t)j * c->Bs);
-    RParArgs a{};
+    a = RParArgs{};
     a.heads = c->heads.as<int32_t>();
     a.tails = c->tails.as<int32_t>();
     a.rels = c->rels.as<int32_t>();
@@ -395,16 +419,7 @@ void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
     a.brel = c->rpar_brel.as<int32_t>() + ib * c->rpar_brel_cap;
     a.nrel = c->pin_bnrel[ib];
     if (a.nrel < 1 || a.nrel > c->rpar_brel_cap) throw std::logic_error("batch relation count out of range");
-    {  // this batch's pair-dedupe table and the next one's (batches alternate)
-        unsigned long long* t0 = c->rpar_ptab.as<unsigned long long>();
-        const size_t sz = (size_t)c->rpar_ptab_mask + 1;
-        // (three tables in rotation: the one a sub-batch's phase A inserts into, the one
-        // phase B of the sub-batch before it may still read, the next one it clears)
-        a.ptab = t0 + (c->batch_stamp % 3) * sz;
-        a.ptab_next = t0 + ((c->batch_stamp + 1) % 3) * sz;
-        a.ptab_mask = c->rpar_ptab_mask;
-    }
-    RParBufs<T> bf{};
+    bf = RParBufs<T>{};
     bf.ent = c->ent.as<T>();
     bf.rel = c->rel.as<T>();
     bf.W = c->w.as<T>();
@@ -416,7 +431,6 @@ void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
     bf.pair = c->rpar_pair.as<T>();
     bf.relpair = c->rpar_relpair.as<T>();
     bf.relpair_stamp = c->rpar_relpair_stamp.as<uint32_t>();
-    bf.stamp = ++c->batch_stamp;
     bf.err = c->dataflow_err.as<uint32_t>() + 1;
     if (c->rpar_mfma) {
         bf.pflag = buf_set(set, c->rpar_pflag, c->sb_pflag).as<uint8_t>();
@@ -438,6 +452,39 @@ void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
         bf.stats = getenv("KB2E_RPAR_STATS") != nullptr;
         bf.last_renorm = 1;
     }
+}
+
+template <typename T>
+void transr_phase_b(kb2e_ctx* c, RParArgs a, RParBufs<T> bf);
+
+// One index batch: sub-batch j of batch b (the whole batch when c->sub == 1).  Phase
+// A (energies, hinge, directions, the matrix partials) reads the tables bfa names
+// -- the start-of-batch copies when the batch runs in sub-batches -- and phase B
+// applies the sub-batch's sums, norms and transRNorm pairs to the live tables.
+template <typename T>
+void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
+    // sub-batches: phase A of sub-batch j >= 1 on its own stream (it reads the
+    // start-of-batch copies, so it runs beside phase B of sub-batch j - 1), its exports
+    // in buffer set j & 1 (the set phase B of sub-batch j - 2 no longer reads); phase A
+    // of sub-batch 0 in line on the batch stream (a wait across queues costs ~12 us:
+    // r23 timeline)
+    const bool ov = c->sub > 1 && sub_overlap_on();
+    const bool side = ov && j > 0;
+    const int set = ov ? (j & 1) : 0;
+    hipStream_t sa = side ? c->suba_stream : c->stream;
+    RParArgs a;
+    RParBufs<T> bf;
+    fill_rpar<T>(c, b, j, set, a, bf);
+    {  // this batch's pair-dedupe table and the next one's (batches alternate)
+        unsigned long long* t0 = c->rpar_ptab.as<unsigned long long>();
+        const size_t sz = (size_t)c->rpar_ptab_mask + 1;
+        // (three tables in rotation: the one a sub-batch's phase A inserts into, the one
+        // phase B of the sub-batch before it may still read, the next one it clears)
+        a.ptab = t0 + (c->batch_stamp % 3) * sz;
+        a.ptab_next = t0 + ((c->batch_stamp + 1) % 3) * sz;
+        a.ptab_mask = c->rpar_ptab_mask;
+    }
+    bf.stamp = ++c->batch_stamp;
     RParBufs<T> bfa = bf;  // phase A's tables: the start-of-batch copies in sub-batch mode
     if (c->sub > 1) {
         bfa.ent = c->snap_ent.as<T>();
@@ -476,12 +523,8 @@ void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
     }
     const size_t lds = rpar_lds<T>(c);
     const int tgrid = c->rpar_max_tiles;
-    const int rel_waves = (int)std::min<int64_t>(c->cfg.num_relations, c->B) * (c->n + 1);
-    const int rgrid = (rel_waves + 3) / 4;
-    const int egrid = 256;
     const bool mf = c->rpar_mfma;
     const size_t lt = mf ? rmfma_lds<T>(c, false) : lds;
-    const size_t lc = mf ? rmfma_lds<T>(c, true) : lds;
     const int tb = mf ? c->rpar_tile_threads : 256;
     auto tile = [&](auto proj, auto grad) {
         constexpr bool P = decltype(proj)::value, G = decltype(grad)::value;
@@ -543,6 +586,22 @@ void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
         }
     });
     a_done();
+    transr_phase_b<T>(c, a, bf);
+    b_done();
+    if (c->pending.size() > 4096) c->flush_timers();
+}
+
+// Phase B of one index batch on the batch stream: its sums, norms and transRNorm pairs
+// applied to the live tables (the tile and chain paths below 128 < n's wide kernels).
+template <typename T>
+void transr_phase_b(kb2e_ctx* c, RParArgs a, RParBufs<T> bf) {
+    // (merged phase A: a sub-batch's tile slots, the next one's follow them)
+    const int tgrid = c->rpar_merge_a ? c->rpar_merge.tcap : c->rpar_max_tiles;
+    const int rel_waves = (int)std::min<int64_t>(c->cfg.num_relations, c->B) * (c->n + 1);
+    const int rgrid = (rel_waves + 3) / 4;
+    const int egrid = 256;
+    const bool mf = c->rpar_mfma;
+    const size_t lc = mf ? rmfma_lds<T>(c, true) : rpar_lds<T>(c);
     // phase B (five kernels) timed as one span, from the first kernel's start
     // to the last one's end; rocprofv3 has the split
     hipEvent_t e0, e1;
@@ -570,7 +629,6 @@ void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
     if (c->rpar_no_constraint) {
         c->ev_end(e1);
         c->launch(rows_fn(yes1()), dim3(fgrid), dim3(1024), 0, e0, e1, a, bf, kRParLongMin, egrid);
-        b_done();
         return;
     }
     if (fuse) {
@@ -608,12 +666,58 @@ void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
         HIPCHK(hipGetLastError());
         c->launch(transr_entity_kernel<T, false>, dim3(egrid), dim3(1024), 0, nullptr, e1, a, bf, kRParLongMin);
     }
-    b_done();
+}
+
+// A batch of sub-batches on the n <= 64 wave path: phase A of all of them once, in line
+// on the live tables -- the values every sub-batch's phase A reads, since no phase B of
+// the batch has run yet -- then phase B of sub-batch 0 .. sub - 1; one stream, no copies.
+// Sub-batch j's exports lie at the strides of rpar_sub_view in the first buffer set.
+template <typename T>
+void run_batch_transr_merged(kb2e_ctx* c, int64_t b) {
+    const RParMerge& m = c->rpar_merge;
+    RParArgs a0;
+    RParBufs<T> bf0;
+    fill_rpar<T>(c, b, 0, 0, a0, bf0);
+    {  // the batch's group of pair-dedupe tables, and the other one, which its inserting launch clears
+        unsigned long long* t0 = c->rpar_ptab.as<unsigned long long>();
+        const size_t gsz = (size_t)m.sub * ((size_t)c->rpar_ptab_mask + 1);
+        const uint32_t grp = c->rpar_merge_batches++ & 1;
+        a0.ptab = t0 + grp * gsz;
+        a0.ptab_next = t0 + (grp ^ 1) * gsz;
+        a0.ptab_mask = c->rpar_ptab_mask;
+    }
+    c->timed("score", [&] {
+        proj_wave_merged_launch<T>(a0, bf0, m, c->stream);
+        if (c->cfg.transr_compat) {
+            const int last = (int)((2 * (int64_t)m.Blast + kScanChunk - 1) / kScanChunk);
+            const int grid = (m.sub - 1) * m.nch + last;
+            rpar_scan_sums_merged_kernel<<<grid, 256, 0, c->stream>>>(a0.proj, m, c->ld, c->n,
+                                                                         c->rpar_scan.as<double>());
+            rpar_scan_energy_merged_kernel<T><<<grid, 1024, rpar_scan_lds(c), c->stream>>>(
+                a0, bf0, m, c->rpar_scan.as<double>(), c->transr_work.as<double>(), c->transr_work_alt.as<double>());
+            HIPCHK(hipGetLastError());
+            std::swap(c->transr_work.p, c->transr_work_alt.p);  // the carried work vectors: one ping-pong a batch
+        }
+        grad_wave_merged_launch<T>(a0, bf0, m, c->stream);
+    });
+    for (int j = 0; j < m.sub; ++j) {
+        RParArgs a = a0;
+        RParBufs<T> bf = bf0;
+        rpar_sub_view(a, bf, m, j);
+        a.nrel = c->pin_bnrel[b * c->sub + j];
+        if (a.nrel < 1 || a.nrel > c->rpar_brel_cap) throw std::logic_error("batch relation count out of range");
+        bf.stamp = ++c->batch_stamp;
+        transr_phase_b<T>(c, a, bf);
+    }
     if (c->pending.size() > 4096) c->flush_timers();
 }
 
 template <typename T>
 void run_batch_transr_parallel(kb2e_ctx* c, int64_t b) {
+    if (c->rpar_merge_a) {
+        run_batch_transr_merged<T>(c, b);
+        return;
+    }
     if (c->sub > 1) {  // the start-of-batch tables for every sub-batch's phase A
         // (made on the side stream beside phase A of sub-batch 0, which then read the live
         // tables, they gained nothing: DESIGN.md section 7 round 8)

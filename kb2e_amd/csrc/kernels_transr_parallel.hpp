@@ -124,10 +124,16 @@ static __attribute__((unused)) __global__ __launch_bounds__(1024) void rel_list_
 // (h', r), (t', r) or (entity[r], r) is the reference's repeated transRNorm
 // call on an already constrained row when an earlier active slot of the batch
 // holds the same (relation, entity) (transr/trainer.cpp:183-188), whichever tile
-// it falls in.  One word per entry, all ones = empty; three tables rotate by
-// sub-batch (phase A runs one sub-batch ahead of phase B): the inserting kernel of
-// sub-batch b fills table b % 3 and clears table (b + 1) % 3, whose last reader was
-// sub-batch b - 2's transRNorm step, while sub-batch b - 1's may still read its own.
+// it falls in.  One word per entry, all ones = empty.  Two rotations, by how
+// phase A is launched:
+//   per sub-batch (phase A one sub-batch ahead of phase B on its own stream): three
+//     tables; the inserting kernel of index batch i fills table i % 3 and clears
+//     table (i + 1) % 3, whose last reader was index batch i - 2's transRNorm step,
+//     while index batch i - 1's may still read its own;
+//   merged (one phase A a batch, RParMerge): two groups of `sub` tables; batch k's
+//     inserting launch fills group k & 1, sub-batch j into table j of it, and every
+//     thread of its grid clears a share of group (k + 1) & 1, whose last reader was
+//     batch k - 1's phase B, earlier on the same stream.
 constexpr int kPtabEntBits = 24, kPtabRelBits = 18, kPtabSlotBits = 22;
 constexpr unsigned long long kPtabEmpty = ~0ull;
 
@@ -229,6 +235,59 @@ struct RParBufs {
 
 __host__ __device__ constexpr int rm_up16_host_dev(int v) { return (v + 15) & ~15; }
 constexpr int kCPairs = 64;  // transRNorm pairs of a tile (4 St + 1 <= 64)
+
+// Merged phase A (n <= 64 wave kernels, sub-batches): one launch of each phase-A
+// kernel covers every sub-batch of the batch.  The arguments beside it are those of
+// sub-batch 0; sub-batch j's are the same at uniform strides -- Bs samples in the
+// sample stream and the per-sample exports, tcap tile slots in the per-tile exports
+// (local tile indices unchanged), one pair-dedupe table, one row of brel -- so phase
+// B of sub-batch j takes the view the block of phase A wrote through.
+struct RParMerge {
+    int32_t sub;       // sub-batches of the batch
+    int32_t Bs;        // samples of each but the last
+    int32_t Blast;     // samples of the last
+    int32_t tcap;      // tile slots of a sub-batch: the blocks it has in a tile launch
+    int32_t nch;       // compat scan: chunks of a full sub-batch (its blocks in a scan launch)
+    int32_t brel_cap;  // row length of brel
+};
+
+template <typename P>
+__host__ __device__ __forceinline__ void rpar_advance(P*& p, int64_t k) {
+    if (p) p += k;
+}
+
+// (a, bf) of sub-batch 0 -> of sub-batch j (a.nrel and bf.stamp are phase B's: the host sets them)
+template <typename T>
+__host__ __device__ __forceinline__ void rpar_sub_view(RParArgs& a, RParBufs<T>& bf, const RParMerge& m, int j) {
+    const int64_t s0 = (int64_t)j * m.Bs, t0 = (int64_t)j * m.tcap;
+    a.B = j == m.sub - 1 ? m.Blast : m.Bs;
+    a.batch += j;
+    rpar_advance(a.si, s0);
+    rpar_advance(a.sj, s0);
+    rpar_advance(a.side, s0);
+    rpar_advance(a.act, s0);
+    rpar_advance(a.loss, s0);
+    rpar_advance(a.proj, s0 * 4 * a.ld);
+    rpar_advance(a.brel, (int64_t)j * m.brel_cap);
+    rpar_advance(a.ptab, (int64_t)j * ((int64_t)a.ptab_mask + 1));
+    rpar_advance(bf.x, s0 * 2 * a.ld);
+    rpar_advance(bf.d, s0 * 2 * a.ld);
+    rpar_advance(bf.y, s0 * 2 * a.ld);
+    rpar_advance(bf.pflag, s0 * 4);
+    rpar_advance(bf.wpart, t0 * bf.cons_ppt * a.n * a.ld);
+    rpar_advance(bf.rpart, t0 * a.ld);
+    rpar_advance(bf.cons_tile, t0 * bf.cons_ppt);
+    rpar_advance(bf.cpairs, t0 * 2 * kCPairs);
+    rpar_advance(bf.vio, t0 * kCPairs);
+    rpar_advance(bf.cnrows, t0);
+}
+
+// The other group's `sub` tables (contiguous at a.ptab_next), cleared by the threads of
+// the merged inserting launch.
+__device__ __forceinline__ void ptab_clear_group(const RParArgs& a, int sub, int64_t tid, int64_t nthreads) {
+    const int64_t words = (int64_t)sub * ((int64_t)a.ptab_mask + 1);
+    for (int64_t q = tid; q < words; q += nthreads) a.ptab_next[q] = kPtabEmpty;
+}
 
 template <typename T>
 __host__ __device__ constexpr int rpar_lds_w(int n, int ld) {
@@ -1009,9 +1068,8 @@ __global__ __launch_bounds__(1024) void transr_rows_kernel(RParArgs a, RParBufs<
 // energies), one thread per (head/tail, element), coalesced rows.
 constexpr int kScanChunk = 64;
 
-static __attribute__((unused)) __global__ __launch_bounds__(256) void rpar_scan_sums_kernel(const double* proj, int64_t calls, int32_t ld,
-                                                             int32_t n, double* sums) {
-    const int c = blockIdx.x;
+__device__ __forceinline__ void rpar_scan_sums_block(const double* proj, int64_t calls, int32_t ld, int32_t n,
+                                                     double* sums, int c) {
     const int64_t c0 = (int64_t)c * kScanChunk, c1 = min<int64_t>(calls, c0 + kScanChunk);
     for (int e = threadIdx.x; e < 2 * n; e += blockDim.x) {
         const int side = e / n, i = e % n;
@@ -1026,6 +1084,20 @@ static __attribute__((unused)) __global__ __launch_bounds__(256) void rpar_scan_
         }
         sums[(int64_t)c * 2 * n + e] = (s[0] + s[1]) + (s[2] + s[3]);
     }
+}
+
+static __attribute__((unused)) __global__ __launch_bounds__(256) void rpar_scan_sums_kernel(const double* proj, int64_t calls, int32_t ld,
+                                                             int32_t n, double* sums) {
+    rpar_scan_sums_block(proj, calls, ld, n, sums, blockIdx.x);
+}
+
+// Merged phase A: block -> (sub-batch j, its chunk); every sub-batch keeps its own
+// chunking (its chunks start at its first call; proj is sub-batch 0's).
+static __attribute__((unused)) __global__ __launch_bounds__(256) void rpar_scan_sums_merged_kernel(const double* proj, RParMerge m, int32_t ld,
+                                                                    int32_t n, double* sums) {
+    const int j = blockIdx.x / m.nch, c = blockIdx.x - j * m.nch;
+    const int64_t calls = 2 * (int64_t)(j == m.sub - 1 ? m.Blast : m.Bs);
+    rpar_scan_sums_block(proj + (int64_t)j * m.Bs * 4 * ld, calls, ld, n, sums + (int64_t)j * m.nch * 2 * n, c);
 }
 
 // Many chunks (K5: 5,000 a batch): the exclusive prefix over the chunks once for
@@ -1078,13 +1150,59 @@ static __attribute__((unused)) __global__ __launch_bounds__(1024) void rpar_scan
 // kScanChunk / 2 samples (transr/transr.cpp:26-35 on the accumulated vectors)
 // and the hinge (common/trainer.cpp:138-141).  The last chunk leaves the work
 // vectors after the batch in work_out (ping-pong with work_in across batches).
-template <typename T>
-__global__ __launch_bounds__(1024) void rpar_scan_energy_kernel(RParArgs a, RParBufs<T> bf, const double* sums,
-                                                                int32_t nchunks, const double* work_in,
-                                                                double* work_out, const double* pre) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double* run_l = (double*)smem;  // [kScanChunk][2 n]
-    const int c = blockIdx.x, n = a.n, ld = a.ld;
+//
+// The pieces, shared with the merged launch's carry-in (below), which must repeat the
+// same additions in the same order:
+// part[g][e]: the sums of chunks [0, c), G thread groups per element, group g over
+// chunks g*16.., (g+G)*16.., sixteen loads in flight (one round trip for FB15k's ~150
+// chunks instead of ten); combined in group order by rpar_scan_start
+__device__ __forceinline__ void rpar_scan_parts(const double* sums, int c, int E2, int G, double* part) {
+    if ((int)threadIdx.x < G * E2) {
+        const int g = threadIdx.x / E2, e = threadIdx.x % E2;
+        double s[4] = {0, 0, 0, 0};
+        for (int q0 = g * 16; q0 < c; q0 += G * 16) {
+            double v[16];
+#pragma unroll
+            for (int q = 0; q < 16; ++q) v[q] = q0 + q < c ? sums[(int64_t)(q0 + q) * E2 + e] : 0.0;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) s[q & 3] += v[q];
+        }
+        part[g * E2 + e] = (s[0] + s[1]) + (s[2] + s[3]);
+    }
+}
+__device__ __forceinline__ double rpar_scan_start(const double* work_in, const double* part, int E2, int G, int e) {
+    double p = 0.0;
+    for (int g = 0; g < G; ++g) p += part[g * E2 + e];
+    return work_in[e] + p;
+}
+// the chunk's calls [c0, c1) added to element e one after another; KEEP: every running
+// value into run_l [call][2 n]
+template <bool KEEP>
+__device__ __forceinline__ double rpar_scan_calls(double run, const double* proj, int64_t c0, int64_t c1, int n,
+                                                  int ld, int e, double* run_l) {
+    const int side = e / n, i = e % n;
+    for (int64_t k = c0; k < c1; k += 16) {
+        double v[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) v[q] = k + q < c1 ? proj[((k + q) * 2 + side) * ld + i] : 0.0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+            if (k + q < c1) {
+                run += v[q];
+                if (KEEP) run_l[(k + q - c0) * 2 * n + e] = run;
+            }
+    }
+    return run;
+}
+
+// chunk c of the nchunks of a's (sub-)batch; work_out null: not the one that leaves the
+// work vectors; clear(): the grid's share of the pair-dedupe table(s) to empty
+template <typename T, class Clear>
+__device__ __forceinline__ void rpar_scan_energy_block(const RParArgs& a, const RParBufs<T>& bf, const double* sums,
+                                                       int c, int32_t nchunks, const double* work_in,
+                                                       double* work_out, const double* pre, double* run_l,
+                                                       Clear clear) {
+    const int n = a.n, ld = a.ld;
     const int64_t calls = 2 * (int64_t)a.B;
     const int64_t c0 = (int64_t)c * kScanChunk, c1 = min<int64_t>(calls, c0 + kScanChunk);
     // the pair-dedupe slots of the chunk's samples (thread 4 q + slot): entity and
@@ -1102,46 +1220,15 @@ __global__ __launch_bounds__(1024) void rpar_scan_energy_kernel(RParArgs a, RPar
         pent = role ? th : hh;
         prel = a.rels[i0];
     }
-    // the sums of all earlier chunks: G thread groups per element, group g over chunks
-    // g*16.., (g+G)*16.., sixteen loads in flight (one round trip for FB15k's ~150
-    // chunks instead of ten), combined in group order
+    // the sums of all earlier chunks
     const int E2 = 2 * n, G = max(1, (int)blockDim.x / E2);
     double* part = run_l + kScanChunk * E2;  // [G][2 n]
-    if (!pre && (int)threadIdx.x < G * E2) {
-        const int g = threadIdx.x / E2, e = threadIdx.x % E2;
-        double s[4] = {0, 0, 0, 0};
-        for (int q0 = g * 16; q0 < c; q0 += G * 16) {
-            double v[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = q0 + q < c ? sums[(int64_t)(q0 + q) * E2 + e] : 0.0;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) s[q & 3] += v[q];
-        }
-        part[g * E2 + e] = (s[0] + s[1]) + (s[2] + s[3]);
-    }
+    if (!pre) rpar_scan_parts(sums, c, E2, G, part);
     __syncthreads();
     for (int e = threadIdx.x; e < 2 * n; e += blockDim.x) {
-        double run;
-        if (pre) {
-            run = pre[(int64_t)c * E2 + e];
-        } else {
-            double p = 0.0;
-            for (int g = 0; g < G; ++g) p += part[g * E2 + e];
-            run = work_in[e] + p;
-        }
-        const int side = e / n, i = e % n;
-        for (int64_t k = c0; k < c1; k += 16) {
-            double v[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = k + q < c1 ? a.proj[((k + q) * 2 + side) * ld + i] : 0.0;
-#pragma unroll
-            for (int q = 0; q < 16; ++q)
-                if (k + q < c1) {
-                    run += v[q];
-                    run_l[(k + q - c0) * 2 * n + e] = run;
-                }
-        }
-        if (c == nchunks - 1) work_out[e] = run;
+        double run = pre ? pre[(int64_t)c * E2 + e] : rpar_scan_start(work_in, part, E2, G, e);
+        run = rpar_scan_calls<true>(run, a.proj, c0, c1, n, ld, e, run_l);
+        if (work_out && c == nchunks - 1) work_out[e] = run;
     }
     __syncthreads();
     const int w = threadIdx.x >> 6, nw = blockDim.x >> 6, l = lane_id();
@@ -1169,10 +1256,74 @@ __global__ __launch_bounds__(1024) void rpar_scan_energy_kernel(RParArgs a, RPar
             act_l[kk - c0 / 2] = active;
         }
     }
-    ptab_clear_next(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    clear();
     __syncthreads();
     if (pent >= 0 && act_l[threadIdx.x >> 2])
         ptab_insert(a, prel, pent, (int)(c0 / 2) * 4 + (int)threadIdx.x);
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void rpar_scan_energy_kernel(RParArgs a, RParBufs<T> bf, const double* sums,
+                                                                int32_t nchunks, const double* work_in,
+                                                                double* work_out, const double* pre) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* run_l = (double*)smem;  // [kScanChunk][2 n]
+    rpar_scan_energy_block<T>(a, bf, sums, blockIdx.x, nchunks, work_in, work_out, pre, run_l, [&] {
+        ptab_clear_next(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    });
+}
+
+// Merged phase A (n <= 64): block -> (sub-batch j, its chunk c).  Sub-batch j's work
+// vectors start from what sub-batch j - 1's last chunk leaves when it runs as a launch
+// of its own: that block's start value (carry-in + the grouped sums of its earlier
+// chunks) and its calls one after another.  Every block of sub-batch j recomputes that
+// chain from sub-batch 0 (work_in) on, the same additions in the same order, into LDS:
+// no serial step between the launches (a one-block carry kernel between the sums and
+// this launch: 16.3 + 9.1 us against 23.3 us this way, FB15k n = 50 at two sub-batches).  (a, bf): sub-batch 0's; sums [sub][m.nch][2 n].
+// The last sub-batch's last chunk leaves the batch's work vectors in work_out.
+// the work vectors sub-batches 1 .. jn start from (see below), one after another: into
+// carry_l (LDS, [2 n]; the returned pointer names the last, work_in when jn == 0);
+// part: [G][2 n] scratch; ends on a barrier when jn > 0
+__device__ __forceinline__ const double* rpar_scan_carry_chain(const double* proj0, const RParMerge& m, int jn, int n,
+                                                               int ld, const double* sums, const double* work_in,
+                                                               double* part, double* carry_l) {
+    const int E2 = 2 * n, G = max(1, (int)blockDim.x / E2);
+    const double* win = work_in;
+    for (int jj = 0; jj < jn; ++jj) {  // (every sub-batch before the last is full: m.nch chunks, m.Bs samples)
+        const int cl = m.nch - 1;
+        const int64_t calls = 2 * (int64_t)m.Bs;
+        const int64_t c0 = (int64_t)cl * kScanChunk, c1 = min<int64_t>(calls, c0 + kScanChunk);
+        rpar_scan_parts(sums + (int64_t)jj * m.nch * E2, cl, E2, G, part);
+        __syncthreads();
+        double run = 0.0;
+        if ((int)threadIdx.x < E2)
+            run = rpar_scan_calls<false>(rpar_scan_start(win, part, E2, G, threadIdx.x),
+                                         proj0 + (int64_t)jj * m.Bs * 4 * ld, c0, c1, n, ld, threadIdx.x, nullptr);
+        __syncthreads();  // (part and carry_l are read: the next step, or the caller, rewrites them)
+        if ((int)threadIdx.x < E2) carry_l[threadIdx.x] = run;
+        win = carry_l;
+    }
+    if (jn > 0) __syncthreads();
+    return win;
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void rpar_scan_energy_merged_kernel(RParArgs a, RParBufs<T> bf, RParMerge m,
+                                                                       const double* sums, const double* work_in,
+                                                                       double* work_out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* run_l = (double*)smem;   // [kScanChunk][2 n]
+    __shared__ double carry_l[128];  // [2 n], n <= 64
+    const int j = blockIdx.x / m.nch, c = blockIdx.x - j * m.nch;
+    const int n = a.n, ld = a.ld, E2 = 2 * n;
+    const double* win =
+        rpar_scan_carry_chain(a.proj, m, j, n, ld, sums, work_in, run_l + kScanChunk * E2, carry_l);
+    rpar_sub_view(a, bf, m, j);
+    const int nchunks = (int)((2 * (int64_t)a.B + kScanChunk - 1) / kScanChunk);
+    rpar_scan_energy_block<T>(a, bf, sums + (int64_t)j * m.nch * E2, c, nchunks, win,
+                              j == m.sub - 1 ? work_out : nullptr, nullptr, run_l, [&] {
+        ptab_clear_group(a, m.sub, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    });
 }
 
 // ---- per-epoch tile index --------------------------------------------------

@@ -50,16 +50,14 @@ __host__ __device__ constexpr int proj_wave_rows(int KS) {
     return sizeof(T) == 8 ? 4 * KS : 16 * ((KS + 3) / 4);
 }
 
+// bid: the block's index among its (sub-)batch's blocks, the local tile
 template <typename T, int KS>
-__global__ __launch_bounds__(128) void transr_proj_wave_kernel(RParArgs a, RParBufs<T> bf) {
+__device__ __forceinline__ void transr_proj_wave_block(const RParArgs& a, const RParBufs<T>& bf, int bid) {
     using M = Mfma16<T>;
     constexpr int NB = (KS + 3) / 4, NP = 16 * NB, L = NP + 2, NS = NP / 4, R = proj_wave_rows<T>(KS);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // fixed energy: this kernel fills the pair-dedupe table (every thread of the grid
-    // clears its share of the next batch's first)
-    if (!a.compat) ptab_clear_next(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
     // the tile from the per-epoch descriptors: two dependent loads to the rows
-    const int t = a.batch_t0[a.batch] + blockIdx.x;
+    const int t = a.batch_t0[a.batch] + bid;
     if (t >= a.batch_t0[a.batch + 1]) return;
     const int r = a.td_r[t], cnt = a.td_cnt[t] & 255;
     const int n = a.n, ld = a.ld;
@@ -172,12 +170,31 @@ __global__ __launch_bounds__(128) void transr_proj_wave_kernel(RParArgs a, RParB
 }
 
 template <typename T, int KS>
-__global__ __launch_bounds__(256) void transr_grad_wave_kernel(RParArgs a, RParBufs<T> bf) {
+__global__ __launch_bounds__(128) void transr_proj_wave_kernel(RParArgs a, RParBufs<T> bf) {
+    // fixed energy: this kernel fills the pair-dedupe table (every thread of the grid
+    // clears its share of the next batch's first)
+    if (!a.compat) ptab_clear_next(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    transr_proj_wave_block<T, KS>(a, bf, blockIdx.x);
+}
+
+// Merged phase A: every sub-batch's tiles in one launch, m.tcap blocks a sub-batch;
+// (a, bf) are sub-batch 0's (rpar_sub_view).
+template <typename T, int KS>
+__global__ __launch_bounds__(128) void transr_proj_wave_merged_kernel(RParArgs a, RParBufs<T> bf, RParMerge m) {
+    if (!a.compat)
+        ptab_clear_group(a, m.sub, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    const int j = blockIdx.x / m.tcap;
+    rpar_sub_view(a, bf, m, j);
+    transr_proj_wave_block<T, KS>(a, bf, blockIdx.x - j * m.tcap);
+}
+
+template <typename T, int KS>
+__device__ __forceinline__ void transr_grad_wave_block(const RParArgs& a, const RParBufs<T>& bf, int bid) {
     using M = Mfma16<T>;
     constexpr int NB = (KS + 3) / 4;
     constexpr int kOut = (NB * NB + kConsWaves - 1) / kConsWaves;  // output tiles per wave
     constexpr int kSteps = 4;  // 2 St <= 16 updates (St <= 8 on the matrix-core path)
-    const int t = a.batch_t0[a.batch] + blockIdx.x;
+    const int t = a.batch_t0[a.batch] + bid;
     if (t >= a.batch_t0[a.batch + 1]) return;
     const int r = a.td_r[t], cnt = a.td_cnt[t] & 255, single = (a.td_cnt[t] >> 8) & 1;
     const int n = a.n, ld = a.ld;
@@ -194,7 +211,7 @@ __global__ __launch_bounds__(256) void transr_grad_wave_kernel(RParArgs a, RParB
         rowu[s] = kk * 2 + side;
         cu[s] = (u < nu && a.act[kk]) ? (T)(-(side ? 1.0 : -1.0) * a.lr) : T(0);
     }
-    T* const wp = bf.wpart + (int64_t)blockIdx.x * n * ld;
+    T* const wp = bf.wpart + (int64_t)bid * n * ld;
 #pragma unroll
     for (int q = 0; q < kOut; ++q) {
         const int tile = w + kConsWaves * q;
@@ -219,7 +236,7 @@ __global__ __launch_bounds__(256) void transr_grad_wave_kernel(RParArgs a, RParB
             typename M::acc_t dr = {T(0), T(0), T(0), T(0)};
 #pragma unroll
             for (int s = 0; s < kSteps; ++s) dr = M::mma(l16 == 0 ? cu[s] : T(0), bv[s], dr);
-            if (M::row(l, 0) == 0 && i < n) bf.rpart[(int64_t)blockIdx.x * ld + i] = dr[0];
+            if (M::row(l, 0) == 0 && i < n) bf.rpart[(int64_t)bid * ld + i] = dr[0];
         }
     }
     if (w == 0) {  // the tile's active updates: lane u holds update u (nu <= 16), one ballot
@@ -267,7 +284,7 @@ __global__ __launch_bounds__(256) void transr_grad_wave_kernel(RParArgs a, RParB
         const bool live = ent >= 0 && !dup;
         const uint64_t m = __ballot(live);
         const int pos = __builtin_popcountll(m & ((1ull << l) - 1));
-        int32_t* cp = bf.cpairs + (int64_t)blockIdx.x * 2 * kCPairs;
+        int32_t* cp = bf.cpairs + (int64_t)bid * 2 * kCPairs;
         if (live) {
             cp[pos] = ent;
             cp[kCPairs + pos] = slot;
@@ -275,8 +292,20 @@ __global__ __launch_bounds__(256) void transr_grad_wave_kernel(RParArgs a, RParB
             bf.pflag[slot] = 0;
         }
         // rows | the relation's only tile | relation, for the transRNorm kernel
-        if (l == 0) bf.cnrows[blockIdx.x] = __builtin_popcountll(m) | (single << 7) | (r << 8);
+        if (l == 0) bf.cnrows[bid] = __builtin_popcountll(m) | (single << 7) | (r << 8);
     }
+}
+
+template <typename T, int KS>
+__global__ __launch_bounds__(256) void transr_grad_wave_kernel(RParArgs a, RParBufs<T> bf) {
+    transr_grad_wave_block<T, KS>(a, bf, blockIdx.x);
+}
+
+template <typename T, int KS>
+__global__ __launch_bounds__(256) void transr_grad_wave_merged_kernel(RParArgs a, RParBufs<T> bf, RParMerge m) {
+    const int j = blockIdx.x / m.tcap;
+    rpar_sub_view(a, bf, m, j);
+    transr_grad_wave_block<T, KS>(a, bf, blockIdx.x - j * m.tcap);
 }
 
 }  // namespace kb2e

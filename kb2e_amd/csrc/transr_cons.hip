@@ -22,7 +22,7 @@ namespace kb2e {
 
 namespace {
 
-enum Kind { kCons, kGrad, kProj };
+enum Kind { kCons, kGrad, kProj, kGradMerged, kProjMerged };
 
 // the chain kernels' grid: a workgroup per relation of the batch (a.brel)
 int chain_grid(const RParArgs& a) { return a.nrel > 0 ? a.nrel : 1; }
@@ -31,7 +31,9 @@ template <typename T, int KS>
 const void* fn_at(Kind k) {
     return k == kCons ? (const void*)transr_cons_wave_kernel<T, KS>
            : k == kGrad ? (const void*)transr_grad_wave_kernel<T, KS>
-                        : (const void*)transr_proj_wave_kernel<T, KS>;
+           : k == kProj ? (const void*)transr_proj_wave_kernel<T, KS>
+           : k == kGradMerged ? (const void*)transr_grad_wave_merged_kernel<T, KS>
+                              : (const void*)transr_proj_wave_merged_kernel<T, KS>;
 }
 
 template <typename T, int... KS>
@@ -180,6 +182,27 @@ void proj_wave_launch(const RParArgs& a, const RParBufs<T>& bf, int grid, hipStr
     HIPCHK(hipLaunchKernel(kernel_fn<T>(kProj, a.n), dim3(grid), dim3(kProjWaves * kWave), args, lds, stream));
 }
 
+template <typename T>
+void proj_wave_merged_launch(const RParArgs& a, const RParBufs<T>& bf, const RParMerge& m, hipStream_t stream) {
+    RParArgs aa = a;
+    RParBufs<T> bb = bf;
+    RParMerge mm = m;
+    void* args[] = {&aa, &bb, &mm};
+    const size_t lds = sizeof(T) * (size_t)proj_wave_rows<T>(cons_live_steps<T>(a.n)) * rm_ld(a.n);
+    HIPCHK(hipLaunchKernel(kernel_fn<T>(kProjMerged, a.n), dim3(m.sub * m.tcap), dim3(kProjWaves * kWave), args, lds,
+                           stream));
+}
+
+template <typename T>
+void grad_wave_merged_launch(const RParArgs& a, const RParBufs<T>& bf, const RParMerge& m, hipStream_t stream) {
+    RParArgs aa = a;
+    RParBufs<T> bb = bf;
+    RParMerge mm = m;
+    void* args[] = {&aa, &bb, &mm};
+    HIPCHK(hipLaunchKernel(kernel_fn<T>(kGradMerged, a.n), dim3(m.sub * m.tcap), dim3(kConsWaves * kWave), args, 0,
+                           stream));
+}
+
 bool cons_chaing_supported(int n) { return n >= 1 && n <= kGenMaxN; }
 
 size_t cons_chaing_setup(int n, int esize) {
@@ -207,6 +230,11 @@ template void proj_wave_launch<float>(const RParArgs&, const RParBufs<float>&, i
 
 template void grad_wave_launch<double>(const RParArgs&, const RParBufs<double>&, int, hipStream_t);
 template void grad_wave_launch<float>(const RParArgs&, const RParBufs<float>&, int, hipStream_t);
+
+template void proj_wave_merged_launch<double>(const RParArgs&, const RParBufs<double>&, const RParMerge&, hipStream_t);
+template void proj_wave_merged_launch<float>(const RParArgs&, const RParBufs<float>&, const RParMerge&, hipStream_t);
+template void grad_wave_merged_launch<double>(const RParArgs&, const RParBufs<double>&, const RParMerge&, hipStream_t);
+template void grad_wave_merged_launch<float>(const RParArgs&, const RParBufs<float>&, const RParMerge&, hipStream_t);
 
 template void cons_wave_launch<double>(const RParArgs&, const RParBufs<double>&, int, size_t, hipStream_t);
 template void cons_wave_launch<float>(const RParArgs&, const RParBufs<float>&, int, size_t, hipStream_t);

@@ -27,6 +27,12 @@ void proj_wave_launch(const RParArgs& a, const RParBufs<T>& bf, int grid, hipStr
 // (kernels_transr_wave.hpp); needs bf.x, bf.d and the hinge decisions in place.
 template <typename T>
 void grad_wave_launch(const RParArgs& a, const RParBufs<T>& bf, int grid, hipStream_t stream);
+// The same two launches once a batch for all its sub-batches (RParMerge; a, bf: sub-batch
+// 0's): m.sub * m.tcap workgroups, sub-batch j's tiles in blocks [j, j + 1) * m.tcap.
+template <typename T>
+void proj_wave_merged_launch(const RParArgs& a, const RParBufs<T>& bf, const RParMerge& m, hipStream_t stream);
+template <typename T>
+void grad_wave_merged_launch(const RParArgs& a, const RParBufs<T>& bf, const RParMerge& m, hipStream_t stream);
 // transRNorm per relation, pair by pair, in chunks of 32 (kernels_transr_pipe.hpp; FP64,
 // n <= 64): dynamic LDS bytes (and the kernel's limit raised to it); the launch, one
 // workgroup per relation of the batch (a.brel, most frequent first), each making its
