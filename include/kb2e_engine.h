@@ -226,7 +226,7 @@ kb2e_status kb2e_evaluate_transr_compat(kb2e_ctx* ctx, const int32_t* heads, con
                                         int64_t nfilter, double* work, double* out,
                                         void (*progress)(double fraction, void* user), void* user);
 
-/* ---- Using a trained model.  The three calls below read the current device
+/* ---- Using a trained model.  The five calls below read the current device
  * tables and change nothing: not the tables, the training state, the RNG or
  * the TransR work vectors.  They use kb2e_evaluate's stateless energies for
  * every model, distance, precision and dim a context takes: FP64 arithmetic
@@ -272,13 +272,47 @@ kb2e_status kb2e_rank_triples(kb2e_ctx* ctx, const int32_t* heads, const int32_t
                               int64_t ntest, const int32_t* filter_heads, const int32_t* filter_tails,
                               const int32_t* filter_relations, int64_t nfilter, int64_t* ranks);
 
+/* Relation prediction: which relation holds between heads[q] and tails[q]?
+ * The candidates of query q are the triples (heads[q], tails[q], r) of every
+ * relation r, each with the energy kb2e_score_triples gives it, bit for bit.
+ * A candidate whose triple is among the nfilter filter triples is excluded and
+ * nothing else is (heads[q] == tails[q] is a legal query).  Output as
+ * kb2e_predict: the k remaining relations of smallest energy in ascending
+ * (energy, relation id) order in ids[q*k + j], energy[q*k + j];
+ * found[q] = min(k, |R| - excluded), which is 0 when every relation of the pair
+ * is in the filter; slots at and after found[q] hold -1 and +inf.
+ * 1 <= k <= 1024 (k may exceed |R|).  KB2E_EINVAL: k out of range, nq < 1, an
+ * id out of range in a query or the filter, NULL arrays with a count > 0.
+ * TransE and TransH score a pair against every relation directly; TransR
+ * projects the distinct entities of the queries once per relation (in relation
+ * batches whose projections stay under 512 MiB; KB2E_RELPRED_REL_BATCH=<n>
+ * lowers the batch) instead of twice per (pair, relation).  The key buffer is
+ * chunked as kb2e_predict's. */
+kb2e_status kb2e_predict_relations(kb2e_ctx* ctx, const int32_t* heads, const int32_t* tails, int64_t nq, int32_t k,
+                                   const int32_t* filter_heads, const int32_t* filter_tails,
+                                   const int32_t* filter_relations, int64_t nfilter, int32_t* ids, double* energy,
+                                   int32_t* found);
+
+/* The rank of the true relation of each test triple, in the caller's order:
+ * ranks[i*2 + 0] = raw rank of relations[i] among the |R| candidates of
+ * (heads[i], tails[i]): 1 + the candidates of strictly smaller energy (ties are
+ * not counted above the truth, as in kb2e_rank_triples); ranks[i*2 + 1] = the
+ * same with the candidates r' != relations[i] whose triple is in the filter
+ * left out.  Mean rank and Hits@1 of these are the relation-prediction numbers
+ * of the PTransE line of work. */
+kb2e_status kb2e_rank_relations(kb2e_ctx* ctx, const int32_t* heads, const int32_t* tails, const int32_t* relations,
+                                int64_t ntest, const int32_t* filter_heads, const int32_t* filter_tails,
+                                const int32_t* filter_relations, int64_t nfilter, int64_t* ranks /* [ntest][2] */);
+
 /* Raw glibc stream access (the context's RNG, as std::rand() in the reference). */
 int32_t kb2e_rng_next(kb2e_ctx* ctx);
 
 /* Timing of the engine's device kernels on the engine's own HIP stream (HIP
  * events around each launch; off by default).  `name` is a kernel family
  * ("score", "fold", "apply", "relowner", "index", "sample", ...; kb2e_predict:
- * "predict_score", "predict_mask", "predict_select").  Returns total
+ * "predict_score", "predict_mask", "predict_select"; kb2e_predict_relations /
+ * kb2e_rank_relations: "relpred_score" (projection + key write), "relpred_mask",
+ * "relpred_select", "relpred_rank").  Returns total
  * milliseconds and launch count since kb2e_profile_enable.  on = 0: off;
  * on = P >= 1: the batch kernels of every P-th batch are timed (event records
  * cost device time of their own; sampling keeps the rest of the run unperturbed),

@@ -1955,6 +1955,38 @@ kb2e_status kb2e_rank_triples(kb2e_ctx* c, const int32_t* th, const int32_t* tt,
     });
 }
 
+kb2e_status kb2e_predict_relations(kb2e_ctx* c, const int32_t* heads, const int32_t* tails, int64_t nq, int32_t k,
+                                   const int32_t* fh, const int32_t* ft, const int32_t* fr, int64_t nfilter,
+                                   int32_t* ids, double* energy, int32_t* found) {
+    return guarded(c, [&] {
+        if (!heads || !tails || nq < 1 || !ids || !energy || !found || nfilter < 0 ||
+            (nfilter > 0 && (!fh || !ft || !fr)))
+            return fail(c, KB2E_EINVAL, "no queries");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        predict_relations(eval_tables(c), RelationQuery{heads, tails, nullptr, nq, k, fh, ft, fr, nfilter}, ids,
+                          energy, found, &hooks);
+        return KB2E_OK;
+    });
+}
+
+kb2e_status kb2e_rank_relations(kb2e_ctx* c, const int32_t* heads, const int32_t* tails, const int32_t* relations,
+                                int64_t ntest, const int32_t* fh, const int32_t* ft, const int32_t* fr,
+                                int64_t nfilter, int64_t* ranks) {
+    return guarded(c, [&] {
+        if (!heads || !tails || !relations || ntest < 1 || !ranks || nfilter < 0 ||
+            (nfilter > 0 && (!fh || !ft || !fr)))
+            return fail(c, KB2E_EINVAL, "empty test set");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        rank_relations(eval_tables(c), RelationQuery{heads, tails, relations, ntest, 0, fh, ft, fr, nfilter}, ranks,
+                       &hooks);
+        return KB2E_OK;
+    });
+}
+
 int32_t kb2e_rng_next(kb2e_ctx* c) {
     if (!c) return -1;
     c->rng_version++;

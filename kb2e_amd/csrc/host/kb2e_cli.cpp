@@ -1,8 +1,8 @@
 // kb2e_cli.cpp -- drop-in command-line front end: trainTransE / trainTransH /
 // trainTransR and evalTransE / evalTransH / evalTransR (dispatch on argv[0]),
 // plus predictTransE / predictTransH / predictTransR (no reference counterpart:
-// top-k answers to (h, ?, r) / (?, t, r) queries from the trained tables;
-// --queries FILE, --topk K, --filtered 0|1).
+// top-k answers to (h, ?, r) / (?, t, r) entity queries and (h, t, ?) relation
+// queries from the trained tables; --queries FILE, --topk K, --filtered 0|1).
 //
 // Same flags, defaults, stdout lines and files as the reference binaries
 // (transe/bin/trainTransE.cpp, common/args.cpp, common/loader.cpp,
@@ -114,7 +114,7 @@ void printUsage(const char* invoked) {  // common/args.cpp:125-142
     printf("   --schedule [0] (GPU: 0 ordered = the reference's sequence, 1 parallel)\n");
     printf("   --gpus [1] (GPU: devices --device .. --device+N-1, triples sharded by head, epoch merge over RCCL)\n");
     printf("   --subbatches [engine default] (GPU, parallel TransR: each batch's updates in this many sub-batches)\n");
-    printf("   --queries FILE (predictTrans*: head<TAB>tail<TAB>relation lines, ? for the unknown head or tail)\n");
+    printf("   --queries FILE (predictTrans*: head<TAB>tail<TAB>relation lines, ? for the unknown head, tail or relation)\n");
     printf("   --topk [10] (predictTrans*)\n");
     printf("   --filtered [1] (predictTrans*: known triples are not answers)\n");
 }
@@ -524,10 +524,13 @@ int eval_main(int argc, char** argv, kb2e_model model) {
 
 // predictTransE|H|R: the reference's flags and files as evalTrans* loads them,
 // plus --queries FILE (lines "head<TAB>tail<TAB>relation" in the triple files'
-// column order with a literal ? for the unknown head or tail), --topk K [10]
-// and --filtered 0|1 [1: known triples (train + valid + test) are not answers].
-// One line per answer: query index (its line in FILE, from 0), position
-// (from 1), entity name, energy.
+// column order with a literal ? for the unknown head or tail, or for the
+// unknown relation: "head<TAB>tail<TAB>?" asks which relation holds), --topk K
+// [10] and --filtered 0|1 [1: known triples (train + valid + test) are not
+// answers].  One line per answer: query index (its line in FILE, from 0),
+// position (from 1), entity (relation) name, energy.  Entity and relation
+// queries may be mixed; the answers come out interleaved, in the order of the
+// queries' lines.
 int predict_main(int argc, char** argv, kb2e_model model) {
     EmbeddingArguments args = parseArgs(argc, argv);
     printf("%s\n", args.to_string().c_str());
@@ -550,12 +553,20 @@ int predict_main(int argc, char** argv, kb2e_model model) {
     std::vector<std::string> names(L.entity2id.size());
     for (const auto& kv : L.entity2id)
         if (kv.second >= 0 && (size_t)kv.second < names.size()) names[(size_t)kv.second] = kv.first;
-    std::vector<int32_t> qe, qr, qs, qline;
+    std::vector<std::string> rnames(L.relation2id.size());
+    for (const auto& kv : L.relation2id)
+        if (kv.second >= 0 && (size_t)kv.second < rnames.size()) rnames[(size_t)kv.second] = kv.first;
+    std::vector<int32_t> qe, qr, qs, qline;  // entity queries
+    std::vector<int32_t> rh, rt, rline;      // relation queries
     char hb[512], tb[512], rb[512];
     for (int line = 0; fscanf(f, "%511s\t%511s\t%511s", hb, tb, rb) == 3; ++line) {
-        const bool noHead = !strcmp(hb, "?"), noTail = !strcmp(tb, "?");
+        const bool noHead = !strcmp(hb, "?"), noTail = !strcmp(tb, "?"), noRel = !strcmp(rb, "?");
         bool fail = false;
-        if (noHead == noTail) {
+        if (noRel && (noHead || noTail)) {
+            std::cout << "Relation query needs both the head and the tail: " << hb << ' ' << tb << std::endl;
+            fail = true;
+        }
+        if (!noRel && noHead == noTail) {
             std::cout << "Query needs exactly one ? in the head or the tail column: " << hb << ' ' << tb << std::endl;
             fail = true;
         }
@@ -567,28 +578,46 @@ int predict_main(int argc, char** argv, kb2e_model model) {
             std::cout << "Tail entity found in triple file that was not found in the identity file: " << tb << std::endl;
             fail = true;
         }
-        if (!L.relation2id.count(rb)) {
+        if (!noRel && !L.relation2id.count(rb)) {
             std::cout << "Relation found in triple file that was not found in the identity file: " << rb << std::endl;
             fail = true;
         }
         if (fail) continue;
-        qe.push_back(L.entity2id[noTail ? hb : tb]);
-        qr.push_back(L.relation2id[rb]);
-        qs.push_back(noTail ? 1 : 0);
-        qline.push_back(line);
+        if (noRel) {
+            rh.push_back(L.entity2id[hb]);
+            rt.push_back(L.entity2id[tb]);
+            rline.push_back(line);
+        } else {
+            qe.push_back(L.entity2id[noTail ? hb : tb]);
+            qr.push_back(L.relation2id[rb]);
+            qs.push_back(noTail ? 1 : 0);
+            qline.push_back(line);
+        }
     }
     fclose(f);
-    if (!qe.empty()) {
-        const size_t nq = qe.size(), k = (size_t)std::max(topk, 1);
-        std::vector<int32_t> ids(nq * k), found(nq);
-        std::vector<double> energy(nq * k);
-        const int64_t nf = filtered ? (int64_t)L.fh.size() : 0;
-        check(L.ctx, kb2e_predict(L.ctx, qe.data(), qr.data(), qs.data(), (int64_t)nq, topk, nf ? L.fh.data() : nullptr,
-                                  nf ? L.ft.data() : nullptr, nf ? L.fr.data() : nullptr, nf, ids.data(),
+    const size_t nq = qe.size(), nrq = rh.size(), k = (size_t)std::max(topk, 1);
+    const int64_t nf = filtered ? (int64_t)L.fh.size() : 0;
+    const int32_t *fh = nf ? L.fh.data() : nullptr, *ft = nf ? L.ft.data() : nullptr, *fr = nf ? L.fr.data() : nullptr;
+    std::vector<int32_t> ids(nq * k), found(nq), rids(nrq * k), rfound(nrq);
+    std::vector<double> energy(nq * k), renergy(nrq * k);
+    if (nq)
+        check(L.ctx, kb2e_predict(L.ctx, qe.data(), qr.data(), qs.data(), (int64_t)nq, topk, fh, ft, fr, nf, ids.data(),
                                   energy.data(), found.data()), "predict");
-        for (size_t q = 0; q < nq; ++q)
+    if (nrq)
+        check(L.ctx, kb2e_predict_relations(L.ctx, rh.data(), rt.data(), (int64_t)nrq, topk, fh, ft, fr, nf,
+                                            rids.data(), renergy.data(), rfound.data()), "predict_relations");
+    // both kinds interleaved, in the order of their lines in FILE
+    for (size_t q = 0, p = 0; q < nq || p < nrq;) {
+        if (p == nrq || (q < nq && qline[q] < rline[p])) {
             for (int j = 0; j < found[q]; ++j)
                 printf("%d\t%d\t%s\t%.6lf\n", qline[q], j + 1, names[(size_t)ids[q * k + j]].c_str(), energy[q * k + j]);
+            ++q;
+        } else {
+            for (int j = 0; j < rfound[p]; ++j)
+                printf("%d\t%d\t%s\t%.6lf\n", rline[p], j + 1, rnames[(size_t)rids[p * k + j]].c_str(),
+                       renergy[p * k + j]);
+            ++p;
+        }
     }
     kb2e_destroy(L.ctx);
     return 0;

@@ -1,5 +1,6 @@
-// predict.hip -- top-k link-prediction queries and triple scoring on the device.
-// Part of libkb2e.so (kb2e_predict, kb2e_score_triples in engine.hip call in here).
+// predict.hip -- top-k link-prediction queries, relation prediction and triple
+// scoring on the device.  Part of libkb2e.so (kb2e_predict, kb2e_score_triples,
+// kb2e_predict_relations, kb2e_rank_relations in engine.hip call in here).
 //
 // A query (e, r, side) asks for the k entities x of smallest energy of
 // (e, x, r) (side 1: the tail is unknown) or (x, e, r) (side 0: the head is),
@@ -27,6 +28,11 @@
 //
 // The key buffer holds a bounded chunk of queries (<= 1 GiB), so a whole test
 // set's queries never need nq x |E| at once.
+//
+// Relation prediction (a pair (h, t) against every relation) writes
+// keys[query][|R|] with kernels of its own -- relpred_direct_kernel for TransE /
+// TransH, relpred_project_kernel + relpred_pair_kernel for TransR -- and shares
+// the mask and the selection; relpred_rank_kernel counts the per-triple ranks.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -399,6 +405,248 @@ __global__ __launch_bounds__(256) void score_triples_transr_kernel(TripleArgs<T>
     }
 }
 
+// ------------------------------------------------------------ relation prediction
+//
+// A query is a pair (h, t) and its candidates are the |R| relations: the keys
+// are keys[query][|R|], every energy the bits score_triples_kernel /
+// score_triples_transr_kernel give for the same triple (the same expressions,
+// each sum serial from zero in the reference's order).
+
+// FP64 transposed copy [n][|R|] of a [|R|][ld] table (relation rows, TransH
+// normals), made once per call: with one thread per relation candidate, the
+// loads of element k of 64 neighbouring relations are then one 512-byte
+// segment instead of 64 rows ld apart, and FP32 tables are widened once.
+template <typename T>
+__global__ __launch_bounds__(256) void relpred_transpose_kernel(const T* src, int32_t n, int32_t ld, int32_t nr,
+                                                                double* dst) {
+    const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= (int64_t)n * nr) return;
+    const int k = (int)(x / nr), r = (int)(x % nr);
+    dst[x] = (double)src[(int64_t)r * ld + k];
+}
+
+template <typename T>
+struct RelDirectArgs {
+    int32_t n, ld, nr, l1;
+    const T* ent;
+    const double* RT;        // [n][nr] relation rows
+    const double* WT;        // [n][nr] TransH normals
+    const int32_t *qh, *qt;  // the chunk's pairs
+    int32_t nq;
+    uint64_t* keys;  // [nq][nr]
+};
+
+// TransE / TransH.  grid.x: relation blocks of 256; grid.y: query tiles of kQ.
+// Dynamic LDS: the tile's head and tail rows widened to FP64, interleaved
+// [kQ][n][2] so that one 16-byte LDS read (a broadcast: every lane reads the
+// same address) gives both.  One thread per relation walks score_triples_kernel's
+// loops for the kQ pairs; the key stores run along the relations (coalesced).
+template <typename T, bool kTransH>
+__global__ __launch_bounds__(256) void relpred_direct_kernel(RelDirectArgs<T> a) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int n = a.n;
+    const int q0 = blockIdx.y * kQ;
+    const int nq = min(kQ, a.nq - q0);
+    for (int x = threadIdx.x; x < kQ * n; x += blockDim.x) {
+        const int q = x / n, k = x % n;
+        const bool in = q < nq;
+        lds[2 * x] = in ? (double)a.ent[(int64_t)a.qh[q0 + q] * a.ld + k] : 0.0;
+        lds[2 * x + 1] = in ? (double)a.ent[(int64_t)a.qt[q0 + q] * a.ld + k] : 0.0;
+    }
+    __syncthreads();
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= a.nr) return;
+    const double2* ht = (const double2*)lds;  // .x head, .y tail
+    double e[kQ];
+#pragma unroll
+    for (int q = 0; q < kQ; ++q) e[q] = 0;
+    if constexpr (!kTransH) {
+        for (int k = 0; k < n; ++k) {
+            const double rv = a.RT[(int64_t)k * a.nr + r];
+#pragma unroll
+            for (int q = 0; q < kQ; ++q) {
+                const double2 p = ht[q * n + k];
+                const double d = p.y - p.x - rv;
+                e[q] += a.l1 ? fabs(d) : d * d;
+            }
+        }
+    } else {
+        double hs[kQ], ts[kQ];
+#pragma unroll
+        for (int q = 0; q < kQ; ++q) hs[q] = ts[q] = 0;
+        for (int k = 0; k < n; ++k) {
+            const double w = a.WT[(int64_t)k * a.nr + r];
+#pragma unroll
+            for (int q = 0; q < kQ; ++q) {
+                const double2 p = ht[q * n + k];
+                hs[q] += w * p.x;
+                ts[q] += w * p.y;
+            }
+        }
+        for (int k = 0; k < n; ++k) {
+            const double w = a.WT[(int64_t)k * a.nr + r];
+            const double rv = a.RT[(int64_t)k * a.nr + r];
+#pragma unroll
+            for (int q = 0; q < kQ; ++q) {
+                const double2 p = ht[q * n + k];
+                e[q] += fabs(p.y - ts[q] * w - (p.x - hs[q] * w) - rv);
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kQ; ++q)
+        if (q < nq) a.keys[(int64_t)(q0 + q) * a.nr + r] = (uint64_t)__double_as_longlong(e[q]);
+}
+
+template <typename T>
+struct RelProjArgs {
+    int32_t n, ld, nu, r0;
+    const T* ent;
+    const T* w;
+    const int32_t* ents;  // [nu] the chunk's distinct entities
+    double* PT;           // [batch][n][nu]
+};
+
+constexpr int kProjK = 8;  // outputs a thread accumulates at once
+
+// TransR.  grid.x: blocks of 256 listed entities; grid.y: the relations of the
+// batch; grid.z: groups of kProjK outputs k.  A thread projects entity ents[u]
+// with relation r0 + blockIdx.y for its group's outputs: eval_project_kernel's
+// sum for each k (the same j order from zero: the bits of
+// score_triples_transr_kernel's hv / tv), kProjK of them side by side, so that
+// each e[j] is loaded once per group instead of once per output.  W_r is read
+// at workgroup-uniform addresses (scalar loads through the scalar cache and
+// L2), not staged in LDS: DESIGN.md 14.  kFull: the group lies inside the row
+// (its kProjK matrix elements of a step are one contiguous run); the ragged
+// last group clamps its column and skips the stores past n.
+template <typename T, bool kFull>
+__device__ __forceinline__ void relpred_project_group(const T* __restrict__ e, const T* __restrict__ W, int n, int ld,
+                                                      int k0, double* __restrict__ out, int64_t nu) {
+    int col[kProjK];
+#pragma unroll
+    for (int c = 0; c < kProjK; ++c) col[c] = kFull ? k0 + c : min(k0 + c, n - 1);
+    double s[kProjK];
+#pragma unroll
+    for (int c = 0; c < kProjK; ++c) s[c] = 0;
+#pragma unroll 2
+    for (int j = 0; j < n; ++j) {
+        const double ej = (double)e[j];
+        const T* wr = W + (int64_t)j * ld;
+#pragma unroll
+        for (int c = 0; c < kProjK; ++c) s[c] += (double)wr[col[c]] * ej;
+    }
+#pragma unroll
+    for (int c = 0; c < kProjK; ++c)
+        if (kFull || k0 + c < n) out[(int64_t)(k0 + c) * nu] = s[c];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void relpred_project_kernel(RelProjArgs<T> a) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= a.nu) return;
+    const int b = blockIdx.y, k0 = blockIdx.z * kProjK;
+    const T* e = a.ent + (int64_t)a.ents[u] * a.ld;
+    const T* W = a.w + (int64_t)(a.r0 + b) * a.n * a.ld;
+    double* out = a.PT + (int64_t)b * a.n * a.nu + u;
+    if (k0 + kProjK <= a.n) relpred_project_group<T, true>(e, W, a.n, a.ld, k0, out, a.nu);
+    else relpred_project_group<T, false>(e, W, a.n, a.ld, k0, out, a.nu);
+}
+
+constexpr int kPairQ = 64;  // pairs per tile: the lanes of a wave
+constexpr int kPairR = 32;  // relations per tile: 256-byte runs of a key row
+
+template <typename T>
+struct RelPairArgs {
+    int32_t n, ld, nu, nr, l1, r0, nb;
+    const T* rel;
+    const double* PT;        // [nb][n][nu]
+    const int32_t *hi, *ti;  // [nq] the pairs as indices into the entity list
+    int32_t nq;
+    uint64_t* keys;  // [nq][nr]
+};
+
+// TransR.  grid.x: tiles of kPairQ pairs; grid.y: tiles of kPairR relations of
+// the batch.  Lanes run along the pairs (the two gathers of a step stay inside
+// one row PT[b][i][.] of the list), each wave takes every fourth relation of the
+// tile: (P_r(t) - P_r(h)) - r term by term, summed over i in order.  The store
+// to keys[q][r] has a stride of |R| * 8 bytes along the lanes; kTranspose turns
+// the tile through LDS so that 32 lanes write one 256-byte run of a key row.
+template <typename T, bool kTranspose>
+__global__ __launch_bounds__(256) void relpred_pair_kernel(RelPairArgs<T> a) {
+    __shared__ uint64_t tile[kTranspose ? kPairQ : 1][kPairR + 1];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int q = blockIdx.x * kPairQ + lane;
+    const bool live = q < a.nq;
+    const int hu = live ? a.hi[q] : 0, tu = live ? a.ti[q] : 0;
+    const int b0 = blockIdx.y * kPairR;
+    for (int rl = wv; rl < kPairR; rl += 4) {
+        const int b = b0 + rl;
+        if (b >= a.nb) break;  // (wave-uniform)
+        const double* P = a.PT + (int64_t)b * a.n * a.nu;
+        const T* rv = a.rel + (int64_t)(a.r0 + b) * a.ld;
+        double e = 0;
+        for (int i = 0; i < a.n; ++i) {
+            const double* row = P + (int64_t)i * a.nu;
+            const double d = row[tu] - row[hu] - (double)rv[i];
+            e += a.l1 ? fabs(d) : d * d;
+        }
+        const uint64_t key = (uint64_t)__double_as_longlong(e);
+        if constexpr (kTranspose) tile[lane][rl] = key;
+        else if (live) a.keys[(int64_t)q * a.nr + a.r0 + b] = key;
+    }
+    if constexpr (kTranspose) {
+        __syncthreads();
+        for (int x = threadIdx.x; x < kPairQ * kPairR; x += blockDim.x) {
+            const int ql = x / kPairR, rl = x % kPairR;
+            const int qq = blockIdx.x * kPairQ + ql, b = b0 + rl;
+            if (qq < a.nq && b < a.nb) a.keys[(int64_t)qq * a.nr + a.r0 + b] = tile[ql][rl];
+        }
+    }
+}
+
+struct RelRankArgs {
+    const uint64_t* keys;  // [rows][nr], not yet masked
+    int32_t nr;
+    const int32_t* truth;  // [rows]
+    const int32_t* group;  // [rows]
+    const int64_t* off;
+    const int32_t* ids;
+    int64_t* ranks;  // [rows][2]
+};
+
+// One workgroup per row: the keys strictly below the truth's are the raw rank;
+// those of the pair's known relations (other than the truth) that are also
+// below it do not count in the filtered one.
+__global__ __launch_bounds__(256) void relpred_rank_kernel(RelRankArgs a) {
+    __shared__ uint32_t part[4][2];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const uint64_t* row = a.keys + (int64_t)blockIdx.x * a.nr;
+    const int tr = a.truth[blockIdx.x];
+    const uint64_t tkey = row[tr];
+    uint32_t below = 0, known = 0;
+    for (int i = threadIdx.x; i < a.nr; i += blockDim.x) below += row[i] < tkey;
+    const int g = a.group[blockIdx.x];
+    for (int64_t j = a.off[g] + threadIdx.x; j < a.off[g + 1]; j += blockDim.x) {
+        const int id = a.ids[j];
+        known += id != tr && row[id] < tkey;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        below += __shfl_down(below, o);
+        known += __shfl_down(known, o);
+    }
+    if (lane == 0) {
+        part[wv][0] = below;
+        part[wv][1] = known;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int64_t b = (int64_t)part[0][0] + part[1][0] + part[2][0] + part[3][0];
+        const int64_t kn = (int64_t)part[0][1] + part[1][1] + part[2][1] + part[3][1];
+        a.ranks[(int64_t)blockIdx.x * 2] = 1 + b;
+        a.ranks[(int64_t)blockIdx.x * 2 + 1] = 1 + b - kn;
+    }
+}
+
 // ------------------------------------------------------------ host side
 
 struct Span {
@@ -583,6 +831,188 @@ void predict_topk(const EvalTables& t, const PredictQuery& q, int32_t* ids, doub
             found[o] = hfound[x - c0];
         }
     }
+}
+
+// ------------------------------------------------------------ relation prediction: host side
+
+namespace {
+
+// The relation batch's projections PT[batch][n][|U|] stay under this: a choice
+// (comfortably inside the card's memory beside the 1 GiB of keys, and large
+// enough that FB15k's 1,345 relations at n = 50 take 16 batches), not the result of a sweep.
+constexpr int64_t kRelPTCapBytes = (int64_t)512 << 20;
+constexpr int64_t kRelMaxBatch = 32768;  // grid.y of the projection kernel
+
+long env_long(const char* name) {
+    const char* v = getenv(name);
+    return v ? atol(v) : 0;
+}
+
+// predict_relations (ids / energy / found) when q.truth is null, else rank_relations (ranks).
+template <typename T>
+void run_relations(const EvalTables& t, const RelationQuery& q, int32_t* ids, double* energy, int32_t* found,
+                   int64_t* ranks, const PredictHooks* hooks) {
+    const int ne = t.ne, nr = t.nr, n = t.n, k = q.k;
+    const bool ranking = q.truth != nullptr;
+    if (q.nq < 1) throw std::invalid_argument("no queries");
+    if (q.nq > INT32_MAX) throw std::invalid_argument("too many queries in one call");
+    if (!ranking && (k < 1 || k > kPredictMaxK))
+        throw std::invalid_argument("k must be in 1.." + std::to_string(kPredictMaxK));
+    for (int64_t x = 0; x < q.nq; ++x)
+        if (q.heads[x] < 0 || q.heads[x] >= ne || q.tails[x] < 0 || q.tails[x] >= ne ||
+            (ranking && (q.truth[x] < 0 || q.truth[x] >= nr)))
+            throw std::invalid_argument("query " + std::to_string(x) + " has an id out of range");
+    for (int64_t x = 0; x < q.nfilter; ++x)
+        if (q.fh[x] < 0 || q.fh[x] >= ne || q.ft[x] < 0 || q.ft[x] >= ne || q.fr[x] < 0 || q.fr[x] >= nr)
+            throw std::invalid_argument("filter triple out of range");
+    const int64_t nq = q.nq;
+    const KnownCandidates kc = build_known_relations(q.heads, q.tails, nq, q.fh, q.ft, q.fr, q.nfilter, ne);
+
+    // rows of the key buffer: predict_topk's rule with the row length |R|
+    int64_t rows = std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)nr * 8));
+    if (const long v = env_long("KB2E_PREDICT_CHUNK_ROWS"); v >= 1) rows = std::min<int64_t>(rows, v);
+    rows = std::min(rows, nq);
+    const size_t staged = kSelScratchBytes + (size_t)nr * 8;
+    const char* kl2 = getenv("KB2E_PREDICT_KEYS_L2");
+    bool keys_lds = staged <= kLdsMax / 4;
+    if (kl2 && kl2[0] == '1') keys_lds = false;
+    if (kl2 && kl2[0] == '0') keys_lds = staged <= kLdsMax;
+    const size_t select_lds = kSelScratchBytes + (keys_lds ? (size_t)nr * 8 : 0);
+    if (!ranking && keys_lds) allow_lds(predict_select_kernel<true>, select_lds);
+
+    const bool transr = t.model == 2;
+    DevBuf d_h, d_t, d_g, d_off, d_kid, d_truth, d_keys, d_RT, d_WT, d_PT, d_ents, d_ids, d_en, d_found, d_ranks;
+    d_g.alloc((size_t)nq * 4);
+    d_off.alloc(kc.off.size() * 8);
+    d_kid.alloc(kc.ids.size() * 4);
+    HIPCHK(hipMemcpyAsync(d_g.p, kc.group.data(), (size_t)nq * 4, hipMemcpyHostToDevice, t.stream));
+    HIPCHK(hipMemcpyAsync(d_off.p, kc.off.data(), kc.off.size() * 8, hipMemcpyHostToDevice, t.stream));
+    if (!kc.ids.empty())
+        HIPCHK(hipMemcpyAsync(d_kid.p, kc.ids.data(), kc.ids.size() * 4, hipMemcpyHostToDevice, t.stream));
+    if (ranking) {
+        d_truth.alloc((size_t)nq * 4);
+        HIPCHK(hipMemcpyAsync(d_truth.p, q.truth, (size_t)nq * 4, hipMemcpyHostToDevice, t.stream));
+        d_ranks.alloc((size_t)rows * 2 * 8);
+    } else {
+        d_ids.alloc((size_t)rows * k * 4);
+        d_en.alloc((size_t)rows * k * 8);
+        d_found.alloc((size_t)rows * 4);
+    }
+    d_keys.alloc((size_t)rows * nr * 8);
+
+    // TransE / TransH: the pairs as entity ids, the relation tables transposed once
+    const size_t direct_lds = (size_t)2 * kQ * n * 8;
+    // TransR: the pairs of a chunk as indices into its entity list (<= 2 * rows, <= |E|)
+    const int64_t umax = std::min<int64_t>(2 * rows, ne);
+    int64_t batch = 1;
+    const bool transpose = !env_on("KB2E_RELPRED_KEYS_STRIDED");
+    if (!transr) {
+        d_h.alloc((size_t)nq * 4);
+        d_t.alloc((size_t)nq * 4);
+        HIPCHK(hipMemcpyAsync(d_h.p, q.heads, (size_t)nq * 4, hipMemcpyHostToDevice, t.stream));
+        HIPCHK(hipMemcpyAsync(d_t.p, q.tails, (size_t)nq * 4, hipMemcpyHostToDevice, t.stream));
+        d_RT.alloc((size_t)n * nr * 8);
+        const unsigned tb = (unsigned)(((int64_t)n * nr + 255) / 256);
+        Span sp(hooks, "relpred_score");
+        relpred_transpose_kernel<T><<<tb, 256, 0, t.stream>>>((const T*)t.rel, n, t.ld, nr, d_RT.as<double>());
+        HIPCHK(hipGetLastError());
+        if (t.model == 1) {
+            d_WT.alloc((size_t)n * nr * 8);
+            relpred_transpose_kernel<T><<<tb, 256, 0, t.stream>>>((const T*)t.w, n, t.ld, nr, d_WT.as<double>());
+            HIPCHK(hipGetLastError());
+            allow_lds(relpred_direct_kernel<T, true>, direct_lds);
+        } else {
+            allow_lds(relpred_direct_kernel<T, false>, direct_lds);
+        }
+        sp.end();
+    } else {
+        d_h.alloc((size_t)rows * 4);  // head / tail indices of the chunk
+        d_t.alloc((size_t)rows * 4);
+        d_ents.alloc((size_t)umax * 4);
+        const int64_t per = (int64_t)n * umax * 8;
+        batch = std::min<int64_t>(std::min<int64_t>(nr, kRelMaxBatch), std::max<int64_t>(1, kRelPTCapBytes / per));
+        if (const long v = env_long("KB2E_RELPRED_REL_BATCH"); v >= 1) batch = std::min<int64_t>(batch, v);
+        d_PT.alloc((size_t)(batch * per));
+    }
+
+    for (int64_t c0 = 0; c0 < nq; c0 += rows) {
+        const int64_t c1 = std::min(nq, c0 + rows);
+        const int32_t m = (int32_t)(c1 - c0);
+        PairEntities pe;  // (lives until the chunk's synchronise: its copies are queued)
+        if (!transr) {
+            Span sp(hooks, "relpred_score");
+            RelDirectArgs<T> da{n, t.ld, nr, t.l1, (const T*)t.ent, d_RT.as<double>(), d_WT.as<double>(),
+                                d_h.as<int32_t>() + c0, d_t.as<int32_t>() + c0, m, d_keys.as<uint64_t>()};
+            dim3 grid((nr + 255) / 256, (unsigned)((m + kQ - 1) / kQ));
+            if (t.model == 1) relpred_direct_kernel<T, true><<<grid, 256, direct_lds, t.stream>>>(da);
+            else relpred_direct_kernel<T, false><<<grid, 256, direct_lds, t.stream>>>(da);
+            HIPCHK(hipGetLastError());
+            sp.end();
+        } else {
+            pe = build_pair_entities(q.heads + c0, q.tails + c0, m);
+            const int32_t nu = (int32_t)pe.ents.size();
+            HIPCHK(hipMemcpyAsync(d_ents.p, pe.ents.data(), (size_t)nu * 4, hipMemcpyHostToDevice, t.stream));
+            HIPCHK(hipMemcpyAsync(d_h.p, pe.hi.data(), (size_t)m * 4, hipMemcpyHostToDevice, t.stream));
+            HIPCHK(hipMemcpyAsync(d_t.p, pe.ti.data(), (size_t)m * 4, hipMemcpyHostToDevice, t.stream));
+            Span sp(hooks, "relpred_score");
+            for (int64_t r0 = 0; r0 < nr; r0 += batch) {  // PT is rebuilt per chunk: its entity list differs
+                const int32_t nb = (int32_t)std::min<int64_t>(batch, nr - r0);
+                RelProjArgs<T> pa{n, t.ld, nu, (int32_t)r0, (const T*)t.ent, (const T*)t.w, d_ents.as<int32_t>(),
+                                  d_PT.as<double>()};
+                relpred_project_kernel<T><<<dim3((nu + 255) / 256, nb, (n + kProjK - 1) / kProjK), 256, 0, t.stream>>>(pa);
+                HIPCHK(hipGetLastError());
+                RelPairArgs<T> ra{n, t.ld, nu, nr, t.l1, (int32_t)r0, nb, (const T*)t.rel, d_PT.as<double>(),
+                                  d_h.as<int32_t>(), d_t.as<int32_t>(), m, d_keys.as<uint64_t>()};
+                dim3 grid((m + kPairQ - 1) / kPairQ, (nb + kPairR - 1) / kPairR);
+                if (transpose) relpred_pair_kernel<T, true><<<grid, 256, 0, t.stream>>>(ra);
+                else relpred_pair_kernel<T, false><<<grid, 256, 0, t.stream>>>(ra);
+                HIPCHK(hipGetLastError());
+            }
+            sp.end();
+        }
+        if (ranking) {
+            Span sp(hooks, "relpred_rank");
+            RelRankArgs ra{d_keys.as<uint64_t>(), nr, d_truth.as<int32_t>() + c0, d_g.as<int32_t>() + c0,
+                           d_off.as<int64_t>(), d_kid.as<int32_t>(), d_ranks.as<int64_t>()};
+            relpred_rank_kernel<<<(unsigned)m, 256, 0, t.stream>>>(ra);
+            HIPCHK(hipGetLastError());
+            sp.end();
+            HIPCHK(hipMemcpyAsync(ranks + c0 * 2, d_ranks.p, (size_t)m * 2 * 8, hipMemcpyDeviceToHost, t.stream));
+        } else {
+            if (!kc.ids.empty()) {
+                Span sp(hooks, "relpred_mask");
+                MaskArgs ma{d_keys.as<uint64_t>(), nr, d_g.as<int32_t>() + c0, d_off.as<int64_t>(), d_kid.as<int32_t>()};
+                predict_mask_kernel<<<(unsigned)m, 256, 0, t.stream>>>(ma);
+                HIPCHK(hipGetLastError());
+                sp.end();
+            }
+            Span sp(hooks, "relpred_select");
+            SelectArgs sa{d_keys.as<uint64_t>(), nr, k, d_ids.as<int32_t>(), d_en.as<double>(), d_found.as<int32_t>()};
+            if (keys_lds) predict_select_kernel<true><<<(unsigned)m, kSelThreads, select_lds, t.stream>>>(sa);
+            else predict_select_kernel<false><<<(unsigned)m, kSelThreads, select_lds, t.stream>>>(sa);
+            HIPCHK(hipGetLastError());
+            sp.end();
+            HIPCHK(hipMemcpyAsync(ids + c0 * k, d_ids.p, (size_t)m * k * 4, hipMemcpyDeviceToHost, t.stream));
+            HIPCHK(hipMemcpyAsync(energy + c0 * k, d_en.p, (size_t)m * k * 8, hipMemcpyDeviceToHost, t.stream));
+            HIPCHK(hipMemcpyAsync(found + c0, d_found.p, (size_t)m * 4, hipMemcpyDeviceToHost, t.stream));
+        }
+        HIPCHK(hipStreamSynchronize(t.stream));
+    }
+}
+
+}  // namespace
+
+void predict_relations(const EvalTables& t, const RelationQuery& q, int32_t* ids, double* energy, int32_t* found,
+                       const PredictHooks* hooks) {
+    if (q.truth) throw std::invalid_argument("predict_relations takes no true relations");
+    if (t.f64) run_relations<double>(t, q, ids, energy, found, nullptr, hooks);
+    else run_relations<float>(t, q, ids, energy, found, nullptr, hooks);
+}
+
+void rank_relations(const EvalTables& t, const RelationQuery& q, int64_t* ranks, const PredictHooks* hooks) {
+    if (!q.truth) throw std::invalid_argument("rank_relations needs the true relations");
+    if (t.f64) run_relations<double>(t, q, nullptr, nullptr, nullptr, ranks, hooks);
+    else run_relations<float>(t, q, nullptr, nullptr, nullptr, ranks, hooks);
 }
 
 }  // namespace kb2e

@@ -1,6 +1,7 @@
 // predict.hpp -- using a trained model on the device: the energy of given
-// triples and the top-k candidates of one-sided queries.  Its own translation
-// unit (predict.hip) behind kb2e_score_triples / kb2e_predict; the stateless
+// triples, the top-k candidates of one-sided queries and relation prediction.
+// Its own translation unit (predict.hip) behind kb2e_score_triples /
+// kb2e_predict / kb2e_predict_relations / kb2e_rank_relations; the stateless
 // FP64 energies are the evaluator's (eval.hpp, eval_shared.hpp).
 #pragma once
 
@@ -39,5 +40,26 @@ void predict_topk(const EvalTables& t, const PredictQuery& q, int32_t* ids, doub
 // energy[i] = tripleEnergy(heads[i], tails[i], relations[i]) (TransR from zeroed work vectors).
 void score_triples(const EvalTables& t, const int32_t* heads, const int32_t* tails, const int32_t* relations,
                    int64_t count, double* energy);
+
+// Relation prediction: query q is the pair (heads[q], tails[q]) and its
+// candidates are the triples (h, t, r) of every relation r.
+struct RelationQuery {
+    const int32_t *heads, *tails;
+    const int32_t* truth;  // rank_relations: the true relation of each pair (else null)
+    int64_t nq;
+    int32_t k;             // predict_relations: 1..kPredictMaxK
+    const int32_t *fh, *ft, *fr;
+    int64_t nfilter;
+};
+
+// ids / energy [nq][k], found [nq]: per pair the found = min(k, |R| - excluded)
+// relations of smallest energy in ascending (energy, id) order, then -1 / +inf.
+void predict_relations(const EvalTables& t, const RelationQuery& q, int32_t* ids, double* energy, int32_t* found,
+                       const PredictHooks* hooks = nullptr);
+
+// ranks[q * 2 + 0..1] = raw and filtered rank of truth[q] among the |R|
+// candidates of pair q (1 + the candidates of strictly smaller energy; the
+// filtered rank leaves out the other relations whose triple is in the filter).
+void rank_relations(const EvalTables& t, const RelationQuery& q, int64_t* ranks, const PredictHooks* hooks = nullptr);
 
 }  // namespace kb2e

@@ -1,5 +1,7 @@
-// predict_host.hpp -- host side of the top-k queries (kb2e_predict), free of
-// HIP so that it can be checked on the CPU (tests/native/predict_check.cpp).
+// predict_host.hpp -- host side of the top-k queries (kb2e_predict) and of
+// relation prediction (kb2e_predict_relations, kb2e_rank_relations), free of
+// HIP so that it can be checked on the CPU (tests/native/predict_check.cpp,
+// tests/native/relpred_check.cpp).
 //
 // A query is (entity e, relation r, side): side 1 asks for tails of (e, ?, r),
 // side 0 for heads of (?, e, r).  The filtered form excludes every candidate x
@@ -67,6 +69,78 @@ inline KnownCandidates build_known_candidates(const int32_t* qe, const int32_t* 
     }
     kc.off.swap(off2);
     return kc;
+}
+
+// ---- relation prediction (kb2e_predict_relations, kb2e_rank_relations): a
+// query is a pair (h, t) and its candidates are the relations.  The known
+// relations of every distinct pair are listed once from the filter triples in
+// the same way: O(nfilter + nq) plus the sort of each list.
+
+inline uint64_t pair_key(int64_t h, int64_t t, int64_t ne) { return (uint64_t)h * (uint64_t)ne + (uint64_t)t; }
+
+// group[q]: the list of query q (queries on the same (h, t) share one); ids: the
+// relations r with (h, t, r) in the filter, ascending and distinct.
+inline KnownCandidates build_known_relations(const int32_t* qh, const int32_t* qt, int64_t nq, const int32_t* fh,
+                                             const int32_t* ft, const int32_t* fr, int64_t nfilter, int64_t ne) {
+    KnownCandidates kc;
+    kc.group.resize((size_t)nq);
+    std::unordered_map<uint64_t, int32_t> groups;
+    groups.reserve((size_t)nq * 2 + 16);
+    for (int64_t q = 0; q < nq; ++q) {
+        auto it = groups.emplace(pair_key(qh[q], qt[q], ne), (int32_t)groups.size()).first;
+        kc.group[(size_t)q] = it->second;
+    }
+    const size_t ng = groups.size();
+    kc.off.assign(ng + 1, 0);
+    std::vector<int32_t> fg((size_t)nfilter);  // the list a filter triple belongs to, -1: no query asks
+    for (int64_t k = 0; k < nfilter; ++k) {
+        auto a = groups.find(pair_key(fh[k], ft[k], ne));
+        fg[(size_t)k] = a == groups.end() ? -1 : a->second;
+        if (fg[(size_t)k] >= 0) ++kc.off[(size_t)fg[(size_t)k] + 1];
+    }
+    for (size_t g = 0; g < ng; ++g) kc.off[g + 1] += kc.off[g];
+    std::vector<int32_t> all((size_t)kc.off[ng]);
+    std::vector<int64_t> fill(kc.off.begin(), kc.off.end() - 1);
+    for (int64_t k = 0; k < nfilter; ++k)
+        if (fg[(size_t)k] >= 0) all[(size_t)fill[(size_t)fg[(size_t)k]]++] = fr[k];
+    // duplicate filter triples: each relation once
+    kc.ids.reserve(all.size());
+    std::vector<int64_t> off2(ng + 1, 0);
+    for (size_t g = 0; g < ng; ++g) {
+        auto b = all.begin() + kc.off[g], e = all.begin() + kc.off[g + 1];
+        std::sort(b, e);
+        e = std::unique(b, e);
+        kc.ids.insert(kc.ids.end(), b, e);
+        off2[g + 1] = (int64_t)kc.ids.size();
+    }
+    kc.off.swap(off2);
+    return kc;
+}
+
+// The distinct entities of a run of pairs, in order of first appearance, and
+// each pair as two indices into that list (TransR projects every listed entity
+// once per relation instead of twice per pair).
+struct PairEntities {
+    std::vector<int32_t> ents;    // [|U|] entity ids
+    std::vector<int32_t> hi, ti;  // [nq] index of the head / tail in ents
+};
+
+inline PairEntities build_pair_entities(const int32_t* qh, const int32_t* qt, int64_t nq) {
+    PairEntities pe;
+    pe.hi.resize((size_t)nq);
+    pe.ti.resize((size_t)nq);
+    std::unordered_map<int32_t, int32_t> slot;
+    slot.reserve((size_t)nq * 2 + 16);
+    auto index = [&](int32_t e) {
+        auto it = slot.emplace(e, (int32_t)pe.ents.size());
+        if (it.second) pe.ents.push_back(e);
+        return it.first->second;
+    };
+    for (int64_t q = 0; q < nq; ++q) {
+        pe.hi[(size_t)q] = index(qh[q]);
+        pe.ti[(size_t)q] = index(qt[q]);
+    }
+    return pe;
 }
 
 }  // namespace kb2e

@@ -29,7 +29,7 @@ EXPORTS = [
     "kb2e_renormalize_rows", "kb2e_init_params_device", "kb2e_write_table", "kb2e_format_table",
     "kb2e_read_table", "kb2e_comm_unique_id", "kb2e_comm_init_rank", "kb2e_comm_init_group", "kb2e_merge_epoch",
     "kb2e_merge_epoch_group", "kb2e_comm_info", "kb2e_get_config", "kb2e_score_triples", "kb2e_predict",
-    "kb2e_rank_triples",
+    "kb2e_rank_triples", "kb2e_predict_relations", "kb2e_rank_relations",
 ]
 COMM_ID_BYTES = 128
 READ_VERBATIM, READ_UNIT, READ_SHRINK = 0, 1, 2
@@ -93,6 +93,8 @@ def lib():
             "kb2e_score_triples": (i32, [vp, i32p, i32p, i32p, i64, dp]),
             "kb2e_predict": (i32, [vp, i32p, i32p, i32p, i64, i32, i32p, i32p, i32p, i64, i32p, dp, i32p]),
             "kb2e_rank_triples": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, C.POINTER(i64)]),
+            "kb2e_predict_relations": (i32, [vp, i32p, i32p, i64, i32, i32p, i32p, i32p, i64, i32p, dp, i32p]),
+            "kb2e_rank_relations": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, C.POINTER(i64)]),
             "kb2e_comm_unique_id": (i32, [u8p]),
             "kb2e_comm_init_rank": (i32, [vp, i32, i32, u8p]),
             "kb2e_comm_init_group": (i32, [C.POINTER(vp), i32]),
@@ -395,6 +397,39 @@ class Engine:
         self._check(lib().kb2e_rank_triples(self.h, _ip(tc[0]), _ip(tc[1]), _ip(tc[2]), len(test),
                                             *[None if c is None else _ip(c) for c in fc], nf,
                                             ranks.ctypes.data_as(C.POINTER(C.c_int64))), "rank_triples")
+        return ranks
+
+    def predict_relations(self, heads, tails, k, filt=None):
+        """Top-k relations of (head, ?, tail) pairs: the candidates of pair q are the
+        triples (heads[q], tails[q], r) of every relation r; those that are a row of
+        `filt` are excluded.  Returns (ids int32[nq, k], energy float64[nq, k],
+        found int32[nq]): ascending (energy, relation id), padded with -1 / +inf
+        after found[q] (0 when every relation of the pair is known)."""
+        h = np.ascontiguousarray(heads, dtype=np.int32).reshape(-1)
+        t = np.ascontiguousarray(tails, dtype=np.int32).reshape(-1)
+        if len(h) != len(t):
+            raise ValueError("heads and tails differ in length")
+        nq, k = len(h), int(k)
+        fc, nf = self._filter_cols(filt)
+        kk = max(k, 1)
+        ids = np.full((nq, kk), -1, np.int32)
+        en = np.full((nq, kk), np.inf)
+        found = np.zeros(nq, np.int32)
+        self._check(lib().kb2e_predict_relations(self.h, _ip(h), _ip(t), nq, k,
+                                                 *[None if c is None else _ip(c) for c in fc], nf, _ip(ids), _dp(en),
+                                                 _ip(found)), "predict_relations")
+        return ids, en, found
+
+    def rank_relations(self, test, filt):
+        """The rank of each test triple's relation among all relations of its
+        (head, tail) pair, in the caller's order: int64[ntest, 2] = raw, filtered."""
+        test = np.ascontiguousarray(test, dtype=np.int32).reshape(-1, 3)
+        tc = [np.ascontiguousarray(test[:, k]) for k in range(3)]
+        fc, nf = self._filter_cols(filt)
+        ranks = np.zeros((len(test), 2), np.int64)
+        self._check(lib().kb2e_rank_relations(self.h, _ip(tc[0]), _ip(tc[1]), _ip(tc[2]), len(test),
+                                              *[None if c is None else _ip(c) for c in fc], nf,
+                                              ranks.ctypes.data_as(C.POINTER(C.c_int64))), "rank_relations")
         return ranks
 
     def device_bytes(self):

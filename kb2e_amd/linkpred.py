@@ -16,7 +16,9 @@ test (tests/test_gpu_hits_parity.py).
 
 ``relation_categories`` / ``hits_by_category`` give the 1-1 / 1-N / N-1 / N-N
 Hits@k table of the TransE, TransH and TransR papers from the per-triple ranks
-of ``Engine.rank_triples``.
+of ``Engine.rank_triples``; ``relation_prediction`` gives the mean rank and
+Hits@k of the true relation (the relation-prediction numbers of the PTransE line
+of work) from ``Engine.rank_relations``.
 """
 from __future__ import annotations
 
@@ -146,3 +148,24 @@ def hits_by_category(ranks, test, cats, at=10):
                      "head": float((ranks[sel, 1] <= at).mean()) if m else None,
                      "tail": float((ranks[sel, 3] <= at).mean()) if m else None}
     return out
+
+
+def relation_metrics(ranks, at=(1, 10)):
+    """Mean rank and Hits@k of ``Engine.rank_relations`` output (columns raw,
+    filtered).  Returns {"count", "raw": {"mean_rank", "hits@k"...}, "filtered": {...}}."""
+    ranks = np.asarray(ranks).reshape(-1, 2)
+    if len(ranks) == 0:
+        raise ValueError("no ranks")
+    out = {"count": int(len(ranks))}
+    for col, name in enumerate(("raw", "filtered")):
+        out[name] = {"mean_rank": float(ranks[:, col].mean()),
+                     **{f"hits@{k}": float((ranks[:, col] <= k).mean()) for k in at}}
+    return out
+
+
+def relation_prediction(eng, test, filt, at=(1, 10)):
+    """Relation prediction over the test triples: the true relation of each
+    (head, tail) pair ranked among all relations on the device
+    (``Engine.rank_relations``), raw and with the other known relations of the
+    pair (rows of `filt`) left out; mean rank and Hits@k for every k of `at`."""
+    return relation_metrics(eng.rank_relations(test, filt), at)
