@@ -304,6 +304,72 @@ kb2e_status kb2e_rank_relations(kb2e_ctx* ctx, const int32_t* heads, const int32
                                 int64_t ntest, const int32_t* filter_heads, const int32_t* filter_tails,
                                 const int32_t* filter_relations, int64_t nfilter, int64_t* ranks /* [ntest][2] */);
 
+/* ---- Triple classification (Socher et al. 2013; TransH 4.3, TransR 4.3): a
+ * triple holds iff its energy is at most the threshold of its relation, fitted
+ * on labelled validation triples.  The three calls below follow the contract of
+ * the block above (read-only, stateless FP64 energies, transr_compat ignored,
+ * every device buffer freed before return, a stream synchronisation at the
+ * end).  Labels are uint8_t: 1 = the triple holds, 0 = it does not. */
+
+/* Fit one threshold per relation.  A triple is classified positive iff
+ * energy <= delta.  The candidates for delta_r are -inf and every energy
+ * (kb2e_score_triples' bits) of relation r's labelled triples; delta_r maximises
+ *     correct(delta) = #{positives with e <= delta} + #{negatives with e > delta}
+ * and among the maxima the smallest delta wins.  thresholds[r] = delta_r,
+ * counts[r*3 + 0..2] = positives, negatives, correct(delta_r) of relation r.
+ * The global threshold is the same fit over all `count` triples with the
+ * relation ignored (*global_threshold, *global_correct; either may be NULL);
+ * a relation without a labelled triple gets thresholds[r] = the global
+ * threshold and counts {0, 0, 0}.  The energies are sorted on the device
+ * (stable LSD radix on (relation, energy bits)) and swept there; nothing about
+ * the result depends on the launch geometry.  KB2E_EINVAL: count < 1 or
+ * count > 2^31 - 1, a label other than 0 / 1, an id out of range, a NULL
+ * array. */
+kb2e_status kb2e_fit_thresholds(kb2e_ctx* ctx, const int32_t* heads, const int32_t* tails, const int32_t* relations,
+                                const uint8_t* labels, int64_t count, double* thresholds /* [R] */,
+                                int64_t* counts /* [R][3] */, double* global_threshold, int64_t* global_correct);
+
+/* labels_out[i] = energy_i <= thresholds[relations[i]] (thresholds has
+ * num_relations entries; -inf and +inf are legal); energy (may be NULL)
+ * receives the energies, bit-identical to kb2e_score_triples.  KB2E_EINVAL:
+ * count < 1, an id out of range, a NULL array. */
+kb2e_status kb2e_classify_triples(kb2e_ctx* ctx, const int32_t* heads, const int32_t* tails,
+                                  const int32_t* relations, int64_t count, const double* thresholds /* [R] */,
+                                  uint8_t* labels_out, double* energy);
+
+/* One negative per positive triple, for data sets that ship none: the head
+ * (slot 0) or the tail (slot 1) of triple i is replaced; the relation stays.
+ * side: 0 replaces the head, 1 the tail, 2 flips a fair coin per triple.
+ * The `known` triples (pass train + valid + test; nknown == 0 with NULL arrays
+ * is legal) give (a) the set of triples that are no negatives and (b) per
+ * (relation, slot) the pool: the distinct entities seen in that slot of that
+ * relation, ascending.  A draw x is rejected if it equals the entity it
+ * replaces or if the new triple is known; x equal to the other slot of the
+ * triple stays legal, as in the reference's corruption loop.
+ *   stage 1 (constrained = 1 and a non-empty pool; the protocol of Socher et
+ *            al. that TransH and TransR use for FB15k): 32 draws from the pool;
+ *   stage 2 (constrained = 0, an empty pool, or stage 1 exhausted): 32 draws
+ *            from all entities.
+ * The first accepted draw is the negative: neg_heads[i], neg_tails[i] are the
+ * new triple's head and tail.  If every draw is rejected both are -1 and the
+ * triple counts in *failed (may be NULL).
+ * The random stream is counter-based and stateless (the context's glibc stream
+ * is not touched), all arithmetic modulo 2^64:
+ *     mix(z):  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *              z *= 0x94D049BB133111EB; z ^= z >> 31          (SplitMix64)
+ *     state   = mix(seed)
+ *     u(i, a) = mix(state + (i << 7) + a)        i = index of the triple
+ *     slot    = side, or for side 2 the top bit of u(i, 0)
+ *     stage 1, draw a = 1..32:   x = pool[u(i, a) % |pool|]
+ *     stage 2, draw a = 33..64:  x = u(i, a) % num_entities
+ * KB2E_EINVAL: count < 1 or count > 2^31 - 1, a side other than 0 / 1 / 2, an
+ * id out of range in the triples or in `known`, a NULL array. */
+kb2e_status kb2e_corrupt_triples(kb2e_ctx* ctx, const int32_t* heads, const int32_t* tails,
+                                 const int32_t* relations, int64_t count, const int32_t* known_heads,
+                                 const int32_t* known_tails, const int32_t* known_relations, int64_t nknown,
+                                 uint64_t seed, int32_t side, int32_t constrained, int32_t* neg_heads,
+                                 int32_t* neg_tails, int64_t* failed);
+
 /* Raw glibc stream access (the context's RNG, as std::rand() in the reference). */
 int32_t kb2e_rng_next(kb2e_ctx* ctx);
 
@@ -312,7 +378,10 @@ int32_t kb2e_rng_next(kb2e_ctx* ctx);
  * ("score", "fold", "apply", "relowner", "index", "sample", ...; kb2e_predict:
  * "predict_score", "predict_mask", "predict_select"; kb2e_predict_relations /
  * kb2e_rank_relations: "relpred_score" (projection + key write), "relpred_mask",
- * "relpred_select", "relpred_rank").  Returns total
+ * "relpred_select", "relpred_rank"; kb2e_fit_thresholds / kb2e_classify_triples:
+ * "classify_score" (energies, and the comparison of kb2e_classify_triples),
+ * "classify_sort" (every radix pass), "classify_fit" (segment starts and both
+ * sweeps); kb2e_corrupt_triples: "classify_corrupt").  Returns total
  * milliseconds and launch count since kb2e_profile_enable.  on = 0: off;
  * on = P >= 1: the batch kernels of every P-th batch are timed (event records
  * cost device time of their own; sampling keeps the rest of the run unperturbed),

@@ -29,6 +29,7 @@
 #include "hip_util.hpp"
 #include "eval.hpp"
 #include "predict.hpp"
+#include "classify.hpp"
 #include "host_data.hpp"
 #include "kernels_common.hpp"
 #include "kernels_index.hpp"
@@ -1983,6 +1984,53 @@ kb2e_status kb2e_rank_relations(kb2e_ctx* c, const int32_t* heads, const int32_t
         const PredictHooks hooks = predict_hooks(c);
         rank_relations(eval_tables(c), RelationQuery{heads, tails, relations, ntest, 0, fh, ft, fr, nfilter}, ranks,
                        &hooks);
+        return KB2E_OK;
+    });
+}
+
+kb2e_status kb2e_fit_thresholds(kb2e_ctx* c, const int32_t* heads, const int32_t* tails, const int32_t* relations,
+                                const uint8_t* labels, int64_t count, double* thresholds, int64_t* counts,
+                                double* global_threshold, int64_t* global_correct) {
+    return guarded(c, [&] {
+        if (!heads || !tails || !relations || !labels || count < 1 || !thresholds || !counts)
+            return fail(c, KB2E_EINVAL, "no labelled triples");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        fit_thresholds(eval_tables(c), LabelledTriples{heads, tails, relations, labels, count}, thresholds, counts,
+                       global_threshold, global_correct, &hooks);
+        return KB2E_OK;
+    });
+}
+
+kb2e_status kb2e_classify_triples(kb2e_ctx* c, const int32_t* heads, const int32_t* tails, const int32_t* relations,
+                                  int64_t count, const double* thresholds, uint8_t* labels_out, double* energy) {
+    return guarded(c, [&] {
+        if (!heads || !tails || !relations || count < 1 || !thresholds || !labels_out)
+            return fail(c, KB2E_EINVAL, "no triples to classify");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        classify_triples(eval_tables(c), heads, tails, relations, count, thresholds, labels_out, energy, &hooks);
+        return KB2E_OK;
+    });
+}
+
+kb2e_status kb2e_corrupt_triples(kb2e_ctx* c, const int32_t* heads, const int32_t* tails, const int32_t* relations,
+                                 int64_t count, const int32_t* kh, const int32_t* kt, const int32_t* kr,
+                                 int64_t nknown, uint64_t seed, int32_t side, int32_t constrained, int32_t* neg_heads,
+                                 int32_t* neg_tails, int64_t* failed) {
+    return guarded(c, [&] {
+        if (!heads || !tails || !relations || count < 1 || !neg_heads || !neg_tails || nknown < 0 ||
+            (nknown > 0 && (!kh || !kt || !kr)))
+            return fail(c, KB2E_EINVAL, "no triples to corrupt");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        const int64_t nf = corrupt_triples(eval_tables(c),
+                                           CorruptQuery{heads, tails, relations, count, kh, kt, kr, nknown, seed, side,
+                                                        constrained},
+                                           neg_heads, neg_tails, &hooks);
+        if (failed) *failed = nf;
         return KB2E_OK;
     });
 }

@@ -2,7 +2,9 @@
 // trainTransR and evalTransE / evalTransH / evalTransR (dispatch on argv[0]),
 // plus predictTransE / predictTransH / predictTransR (no reference counterpart:
 // top-k answers to (h, ?, r) / (?, t, r) entity queries and (h, t, ?) relation
-// queries from the trained tables; --queries FILE, --topk K, --filtered 0|1).
+// queries from the trained tables; --queries FILE, --topk K, --filtered 0|1)
+// and classifyTransE / classifyTransH / classifyTransR (triple classification:
+// thresholds fitted on the valid split, accuracy on the test split).
 //
 // Same flags, defaults, stdout lines and files as the reference binaries
 // (transe/bin/trainTransE.cpp, common/args.cpp, common/loader.cpp,
@@ -30,6 +32,7 @@
 #include <vector>
 
 #include "../../../include/kb2e_engine.h"
+#include "../classify_host.hpp"
 
 namespace kb2e_host {
 
@@ -117,6 +120,11 @@ void printUsage(const char* invoked) {  // common/args.cpp:125-142
     printf("   --queries FILE (predictTrans*: head<TAB>tail<TAB>relation lines, ? for the unknown head, tail or relation)\n");
     printf("   --topk [10] (predictTrans*)\n");
     printf("   --filtered [1] (predictTrans*: known triples are not answers)\n");
+    printf("   --negseed [0] (classifyTrans*: seed of the generated negatives; the test split uses seed + 1)\n");
+    printf("   --constrained [1] (classifyTrans*: negatives from the entities seen in that slot of the relation)\n");
+    printf("   --validlabels FILE (classifyTrans*: head<TAB>tail<TAB>relation<TAB>label lines, 1 / -1 or 0; instead of generated negatives)\n");
+    printf("   --testlabels FILE (classifyTrans*: likewise for the test split)\n");
+    printf("   --out FILE (classifyTrans*: label<TAB>energy of every classified test triple)\n");
 }
 
 EmbeddingArguments parseArgs(int argc, char** argv) {  // common/args.cpp:53-122
@@ -623,6 +631,126 @@ int predict_main(int argc, char** argv, kb2e_model model) {
     return 0;
 }
 
+// classifyTransE|H|R: triple classification (Socher et al. 2013; TransH 4.3,
+// TransR 4.3) of the tables evalTrans* loads.  Per-relation thresholds are
+// fitted on the valid split and applied to the test split.  A split is either
+// a labelled file (--validlabels / --testlabels: "head<TAB>tail<TAB>relation
+// <TAB>label", 1 positive, -1 or 0 negative) or the split's triples followed by
+// one generated negative each (kb2e_corrupt_triples with known = test + train +
+// valid, a coin per triple, --constrained [1], seed --negseed [0] for valid and
+// seed + 1 for test; negatives that could not be drawn are dropped).  One line
+// per relation with test triples: relation, threshold, valid accuracy ("nan"
+// without a valid triple: the global threshold is used), test count, test
+// accuracy; then the overall test accuracy.  --out FILE: predicted label and
+// energy of every classified test triple, in the order of the list (the test
+// triples, then their generated negatives).
+struct LabelledList {
+    std::vector<int32_t> h, t, r;
+    std::vector<uint8_t> label;
+    void add(int hh, int tt, int rr, int ll) {
+        h.push_back(hh);
+        t.push_back(tt);
+        r.push_back(rr);
+        label.push_back((uint8_t)ll);
+    }
+};
+
+int classify_main(int argc, char** argv, kb2e_model model) {
+    EmbeddingArguments args = parseArgs(argc, argv);
+    printf("%s\n", args.to_string().c_str());
+    int i, constrained = 1;
+    unsigned long long negseed = 0;
+    std::string labelFile[2], outPath;
+    if ((i = argpos("negseed", true, argc, argv)) != -1) negseed = strtoull(argv[i + 1], nullptr, 10);
+    if ((i = argpos("constrained", true, argc, argv)) != -1) constrained = atoi(argv[i + 1]) ? 1 : 0;
+    if ((i = argpos("validlabels", true, argc, argv)) != -1) labelFile[0] = argv[i + 1];
+    if ((i = argpos("testlabels", true, argc, argv)) != -1) labelFile[1] = argv[i + 1];
+    if ((i = argpos("out", true, argc, argv)) != -1) outPath = argv[i + 1];
+    LoadedModel L;
+    load_model(args, model, L);
+    kb2e_ctx* ctx = L.ctx;
+    const int nr = (int)L.relation2id.size();
+    std::vector<std::string> rnames((size_t)nr);
+    for (const auto& kv : L.relation2id)
+        if (kv.second >= 0 && kv.second < nr) rnames[(size_t)kv.second] = kv.first;
+
+    LabelledList split[2];  // valid, test
+    for (int s = 0; s < 2; ++s) {
+        LabelledList& S = split[s];
+        if (!labelFile[s].empty()) {
+            if (!kb2e::load_labelled_file(labelFile[s], L.entity2id, L.relation2id,
+                                          [&](int h, int t, int r, int l) { S.add(h, t, r, l); })) {
+                printf("Could not open labelled triple file: %s\n", labelFile[s].c_str());
+                exit(2);
+            }
+        } else {
+            if (s == 0)
+                loadTripleFile(args.dataDir + "/valid.txt", L.entity2id, L.relation2id,
+                               [&](int h, int t, int r) { S.add(h, t, r, 1); });
+            else
+                for (size_t k = 0; k < L.th.size(); ++k) S.add(L.th[k], L.tt[k], L.tr[k], 1);
+            const size_t np = S.h.size();
+            if (np) {
+                std::vector<int32_t> nh(np), nt(np);
+                int64_t failed = 0;
+                check(ctx, kb2e_corrupt_triples(ctx, S.h.data(), S.t.data(), S.r.data(), (int64_t)np, L.fh.data(),
+                                                L.ft.data(), L.fr.data(), (int64_t)L.fh.size(), negseed + (unsigned)s, 2,
+                                                constrained, nh.data(), nt.data(), &failed), "corrupt_triples");
+                if (failed)
+                    printf("%lld %s negatives could not be drawn and are left out\n", (long long)failed,
+                           s == 0 ? "valid" : "test");
+                for (size_t k = 0; k < np; ++k)
+                    if (nh[k] >= 0) S.add(nh[k], nt[k], S.r[k], 0);
+            }
+        }
+        if (S.h.empty()) {
+            printf("No %s triples to classify\n", s == 0 ? "valid" : "test");
+            exit(1);
+        }
+    }
+    std::vector<double> thr((size_t)nr);
+    std::vector<int64_t> counts((size_t)nr * 3);
+    double gthr = 0;
+    int64_t gcorrect = 0;
+    check(ctx, kb2e_fit_thresholds(ctx, split[0].h.data(), split[0].t.data(), split[0].r.data(), split[0].label.data(),
+                                   (int64_t)split[0].h.size(), thr.data(), counts.data(), &gthr, &gcorrect),
+          "fit_thresholds");
+    const LabelledList& T = split[1];
+    std::vector<uint8_t> predicted(T.h.size());
+    std::vector<double> energy(T.h.size());
+    check(ctx, kb2e_classify_triples(ctx, T.h.data(), T.t.data(), T.r.data(), (int64_t)T.h.size(), thr.data(),
+                                     predicted.data(), energy.data()), "classify_triples");
+    std::vector<int64_t> n((size_t)nr, 0), ok((size_t)nr, 0);
+    int64_t total_ok = 0;
+    for (size_t k = 0; k < T.h.size(); ++k) {
+        ++n[(size_t)T.r[k]];
+        if (predicted[k] == T.label[k]) {
+            ++ok[(size_t)T.r[k]];
+            ++total_ok;
+        }
+    }
+    for (int r = 0; r < nr; ++r) {
+        if (!n[(size_t)r]) continue;
+        const int64_t nv = counts[(size_t)r * 3] + counts[(size_t)r * 3 + 1];
+        printf("%s\t%.6lf\t", rnames[(size_t)r].c_str(), thr[(size_t)r]);
+        if (nv) printf("%.6lf", (double)counts[(size_t)r * 3 + 2] / (double)nv);
+        else printf("nan");
+        printf("\t%lld\t%.6lf\n", (long long)n[(size_t)r], (double)ok[(size_t)r] / (double)n[(size_t)r]);
+    }
+    printf("accuracy: %.6lf (%lld triples)\n", (double)total_ok / (double)T.h.size(), (long long)T.h.size());
+    if (!outPath.empty()) {
+        FILE* f = fopen(outPath.c_str(), "w");
+        if (!f) {
+            printf("Could not open output file: %s\n", outPath.c_str());
+            exit(1);
+        }
+        for (size_t k = 0; k < T.h.size(); ++k) fprintf(f, "%d\t%.6lf\n", (int)predicted[k], energy[k]);
+        fclose(f);
+    }
+    kb2e_destroy(ctx);
+    return 0;
+}
+
 }  // namespace kb2e_host
 
 #ifndef KB2E_CLI_NO_MAIN  // (tests/native/host_check.cpp includes this file for its parser and loader)
@@ -640,7 +768,11 @@ int main(int argc, char** argv) {
     if (prog == "predictTransE") return predict_main(argc, argv, KB2E_TRANSE);
     if (prog == "predictTransH") return predict_main(argc, argv, KB2E_TRANSH);
     if (prog == "predictTransR") return predict_main(argc, argv, KB2E_TRANSR);
-    fprintf(stderr, "invoke as trainTransE|H|R, evalTransE|H|R or predictTransE|H|R (got %s)\n", prog.c_str());
+    if (prog == "classifyTransE") return classify_main(argc, argv, KB2E_TRANSE);
+    if (prog == "classifyTransH") return classify_main(argc, argv, KB2E_TRANSH);
+    if (prog == "classifyTransR") return classify_main(argc, argv, KB2E_TRANSR);
+    fprintf(stderr, "invoke as trainTransE|H|R, evalTransE|H|R, predictTransE|H|R or classifyTransE|H|R (got %s)\n",
+            prog.c_str());
     return 2;
 }
 #endif

@@ -649,19 +649,6 @@ __global__ __launch_bounds__(256) void relpred_rank_kernel(RelRankArgs a) {
 
 // ------------------------------------------------------------ host side
 
-struct Span {
-    const PredictHooks* h;
-    const char* name;
-    hipEvent_t a = nullptr;
-    Span(const PredictHooks* hooks, const char* nm) : h(hooks), name(nm) {
-        if (h && h->begin) a = h->begin(h->ud);
-    }
-    void end() {
-        if (h && h->end && a) h->end(h->ud, name, a);
-        a = nullptr;
-    }
-};
-
 bool env_on(const char* name) {
     const char* v = getenv(name);
     return v && v[0] == '1';
@@ -681,6 +668,16 @@ void run_score_triples(const EvalTables& t, const int32_t* dh, const int32_t* dt
 }
 
 }  // namespace
+
+void score_triples_device(const EvalTables& t, const int32_t* dh, const int32_t* dt, const int32_t* dr, int64_t count,
+                          double* dout) {
+    const int64_t chunk = (int64_t)1 << 22;
+    for (int64_t c0 = 0; c0 < count; c0 += chunk) {
+        const int32_t m = (int32_t)std::min(chunk, count - c0);
+        if (t.f64) run_score_triples<double>(t, dh + c0, dt + c0, dr + c0, m, dout + c0);
+        else run_score_triples<float>(t, dh + c0, dt + c0, dr + c0, m, dout + c0);
+    }
+}
 
 void score_triples(const EvalTables& t, const int32_t* heads, const int32_t* tails, const int32_t* relations,
                    int64_t count, double* energy) {

@@ -22,6 +22,20 @@ struct PredictHooks {
     void (*end)(void* ud, const char* name, hipEvent_t a);
 };
 
+// One timed span of a kernel family (nothing when hooks are null or profiling is off).
+struct Span {
+    const PredictHooks* h;
+    const char* name;
+    hipEvent_t a = nullptr;
+    Span(const PredictHooks* hooks, const char* nm) : h(hooks), name(nm) {
+        if (h && h->begin) a = h->begin(h->ud);
+    }
+    void end() {
+        if (h && h->end && a) h->end(h->ud, name, a);
+        a = nullptr;
+    }
+};
+
 struct PredictQuery {
     const int32_t *ent, *rel, *side;  // query q: (ent[q], ?, rel[q]) for side 1, (?, ent[q], rel[q]) for side 0
     int64_t nq;
@@ -40,6 +54,13 @@ void predict_topk(const EvalTables& t, const PredictQuery& q, int32_t* ids, doub
 // energy[i] = tripleEnergy(heads[i], tails[i], relations[i]) (TransR from zeroed work vectors).
 void score_triples(const EvalTables& t, const int32_t* heads, const int32_t* tails, const int32_t* relations,
                    int64_t count, double* energy);
+
+// The same kernels on arrays that are already on the device (classify.hip: the
+// energies never leave the card between scoring and fitting).  The ids must be
+// in range (the caller checks them on the host).  Queued on t.stream in
+// launches of at most 2^22 triples; no synchronisation.
+void score_triples_device(const EvalTables& t, const int32_t* d_heads, const int32_t* d_tails,
+                          const int32_t* d_relations, int64_t count, double* d_energy);
 
 // Relation prediction: query q is the pair (heads[q], tails[q]) and its
 // candidates are the triples (h, t, r) of every relation r.

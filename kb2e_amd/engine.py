@@ -29,7 +29,8 @@ EXPORTS = [
     "kb2e_renormalize_rows", "kb2e_init_params_device", "kb2e_write_table", "kb2e_format_table",
     "kb2e_read_table", "kb2e_comm_unique_id", "kb2e_comm_init_rank", "kb2e_comm_init_group", "kb2e_merge_epoch",
     "kb2e_merge_epoch_group", "kb2e_comm_info", "kb2e_get_config", "kb2e_score_triples", "kb2e_predict",
-    "kb2e_rank_triples", "kb2e_predict_relations", "kb2e_rank_relations",
+    "kb2e_rank_triples", "kb2e_predict_relations", "kb2e_rank_relations", "kb2e_fit_thresholds",
+    "kb2e_classify_triples", "kb2e_corrupt_triples",
 ]
 COMM_ID_BYTES = 128
 READ_VERBATIM, READ_UNIT, READ_SHRINK = 0, 1, 2
@@ -95,6 +96,10 @@ def lib():
             "kb2e_rank_triples": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, C.POINTER(i64)]),
             "kb2e_predict_relations": (i32, [vp, i32p, i32p, i64, i32, i32p, i32p, i32p, i64, i32p, dp, i32p]),
             "kb2e_rank_relations": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, C.POINTER(i64)]),
+            "kb2e_fit_thresholds": (i32, [vp, i32p, i32p, i32p, u8p, i64, dp, C.POINTER(i64), dp, C.POINTER(i64)]),
+            "kb2e_classify_triples": (i32, [vp, i32p, i32p, i32p, i64, dp, u8p, dp]),
+            "kb2e_corrupt_triples": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, C.c_uint64, i32, i32,
+                                           i32p, i32p, C.POINTER(i64)]),
             "kb2e_comm_unique_id": (i32, [u8p]),
             "kb2e_comm_init_rank": (i32, [vp, i32, i32, u8p]),
             "kb2e_comm_init_group": (i32, [C.POINTER(vp), i32]),
@@ -431,6 +436,65 @@ class Engine:
                                               *[None if c is None else _ip(c) for c in fc], nf,
                                               ranks.ctypes.data_as(C.POINTER(C.c_int64))), "rank_relations")
         return ranks
+
+    # ------------------------------------------------ triple classification
+    def fit_thresholds(self, triples, labels):
+        """Per-relation energy thresholds fitted on labelled (head, tail, relation)
+        rows (label 1: the triple holds, 0: it does not); a triple is positive iff
+        energy <= threshold.  Returns (thresholds float64[R], counts int64[R, 3] =
+        positives, negatives, correctly classified per relation, global_threshold,
+        global_correct); a relation without a labelled triple gets the global
+        threshold and counts 0 (the rule: include/kb2e_engine.h)."""
+        t = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+        lab = np.ascontiguousarray(labels).reshape(-1)
+        if len(lab) != len(t):
+            raise ValueError("triples and labels differ in length")
+        if len(lab) and (lab.min() < 0 or lab.max() > 255):
+            raise EngineError("fit_thresholds: EINVAL: a label is neither 0 nor 1")
+        lab = np.ascontiguousarray(lab, dtype=np.uint8)
+        cols = [np.ascontiguousarray(t[:, k]) for k in range(3)]
+        thr = np.zeros(self.nr)
+        counts = np.zeros((self.nr, 3), np.int64)
+        gthr, gcorrect = C.c_double(0), C.c_int64(0)
+        self._check(lib().kb2e_fit_thresholds(self.h, _ip(cols[0]), _ip(cols[1]), _ip(cols[2]),
+                                              lab.ctypes.data_as(C.POINTER(C.c_uint8)), len(t), _dp(thr),
+                                              counts.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(gthr),
+                                              C.byref(gcorrect)), "fit_thresholds")
+        return thr, counts, gthr.value, gcorrect.value
+
+    def classify(self, triples, thresholds, with_energy=False):
+        """labels uint8[count]: 1 where energy <= thresholds[relation] (float64[R],
+        +-inf allowed); with_energy=True also returns the energies (score()'s bits)."""
+        t = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        if len(thr) != self.nr:
+            raise EngineError(f"classify: EINVAL: {len(thr)} thresholds for {self.nr} relations")
+        cols = [np.ascontiguousarray(t[:, k]) for k in range(3)]
+        out = np.zeros(len(t), np.uint8)
+        en = np.zeros(len(t)) if with_energy else None
+        self._check(lib().kb2e_classify_triples(self.h, _ip(cols[0]), _ip(cols[1]), _ip(cols[2]), len(t), _dp(thr),
+                                                out.ctypes.data_as(C.POINTER(C.c_uint8)), _dp(en)), "classify_triples")
+        return (out, en) if with_energy else out
+
+    def corrupt(self, triples, known, seed=0, side=2, constrained=True):
+        """One negative per row of `triples`: the head (side 0), the tail (side 1) or
+        one of them by a fair coin (side 2) replaced, drawn from the entities seen
+        in that slot of that relation among the rows of `known` (constrained, then
+        from all entities), never equal to the replaced entity and never a row of
+        `known`.  Returns (negatives int32[count, 3], failed): a row is (-1, -1,
+        relation) where every draw was rejected.  The stream is a function of
+        (seed, row index) alone (include/kb2e_engine.h kb2e_corrupt_triples)."""
+        t = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+        cols = [np.ascontiguousarray(t[:, k]) for k in range(3)]
+        kc, nk = self._filter_cols(known)
+        nh = np.full(len(t), -1, np.int32)
+        nt = np.full(len(t), -1, np.int32)
+        failed = C.c_int64(0)
+        self._check(lib().kb2e_corrupt_triples(self.h, _ip(cols[0]), _ip(cols[1]), _ip(cols[2]), len(t),
+                                               *[None if c is None else _ip(c) for c in kc], nk,
+                                               C.c_uint64(int(seed) & (2 ** 64 - 1)), int(side), int(bool(constrained)),
+                                               _ip(nh), _ip(nt), C.byref(failed)), "corrupt_triples")
+        return np.stack([nh, nt, cols[2]], axis=1), failed.value
 
     def device_bytes(self):
         return lib().kb2e_device_bytes(self.h)

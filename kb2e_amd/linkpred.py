@@ -18,7 +18,12 @@ test (tests/test_gpu_hits_parity.py).
 Hits@k table of the TransE, TransH and TransR papers from the per-triple ranks
 of ``Engine.rank_triples``; ``relation_prediction`` gives the mean rank and
 Hits@k of the true relation (the relation-prediction numbers of the PTransE line
-of work) from ``Engine.rank_relations``.
+of work) from ``Engine.rank_relations``.  ``triple_classification`` is the third
+evaluation task of those papers (Socher et al. 2013; TransH 4.3, TransR 4.3):
+per-relation energy thresholds fitted on the validation split
+(``Engine.fit_thresholds``), negatives generated on the device where the data
+set ships none (``Engine.corrupt``), accuracy on the test split
+(``Engine.classify``).
 """
 from __future__ import annotations
 
@@ -169,3 +174,54 @@ def relation_prediction(eng, test, filt, at=(1, 10)):
     (``Engine.rank_relations``), raw and with the other known relations of the
     pair (rows of `filt`) left out; mean rank and Hits@k for every k of `at`."""
     return relation_metrics(eng.rank_relations(test, filt), at)
+
+
+def _labelled_split(eng, given, positives, known, seed, constrained):
+    """(triples, labels, failed): the caller's labelled pair, or the positives
+    followed by one generated negative each (failed ones dropped)."""
+    if given is not None:
+        triples, labels = given
+        triples = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 3)
+        labels = np.ascontiguousarray(labels, dtype=np.uint8).reshape(-1)
+        if len(triples) != len(labels):
+            raise ValueError("triples and labels differ in length")
+        return triples, labels, 0
+    positives = np.ascontiguousarray(positives, dtype=np.int32).reshape(-1, 3)
+    neg, failed = eng.corrupt(positives, known, seed=seed, side=2, constrained=constrained)
+    neg = neg[neg[:, 0] >= 0]
+    triples = np.concatenate([positives, neg]).astype(np.int32)
+    labels = np.concatenate([np.ones(len(positives), np.uint8), np.zeros(len(neg), np.uint8)])
+    return triples, labels, int(failed)
+
+
+def classification_accuracy(predicted, labels, relations, num_relations):
+    """{"count", "accuracy", "per_relation": {r: {"count", "accuracy"}}} of predicted
+    against true labels; only relations with a triple are listed."""
+    predicted, labels, relations = (np.asarray(a).reshape(-1) for a in (predicted, labels, relations))
+    hit = predicted == labels
+    n = np.bincount(relations, minlength=num_relations)
+    ok = np.bincount(relations, weights=hit, minlength=num_relations).astype(np.int64)
+    return {"count": int(len(hit)), "accuracy": float(hit.sum() / len(hit)) if len(hit) else None,
+            "per_relation": {int(r): {"count": int(n[r]), "accuracy": float(ok[r] / n[r])}
+                             for r in np.flatnonzero(n)}}
+
+
+def triple_classification(eng, ds, *, seed=0, constrained=True, valid=None, test=None):
+    """Triple classification of a trained engine: thresholds fitted on the valid
+    split, accuracy on the test split.  `valid` / `test` are optional (triples,
+    labels) pairs for data sets that ship labels (WN11, FB13); otherwise one
+    negative per triple of ``ds.valid`` / ``ds.test`` is generated with
+    known = train + valid + test (stream seeds `seed` and `seed + 1`), failed
+    ones dropped.  Returns {"thresholds", "counts", "global_threshold",
+    "global_correct", "valid": {...}, "test": {...}}, each split with "count",
+    "accuracy", "per_relation" and "failed"."""
+    known = np.concatenate([ds.train, ds.valid, ds.test])
+    vt, vl, vfail = _labelled_split(eng, valid, ds.valid, known, seed, constrained)
+    tt, tl, tfail = _labelled_split(eng, test, ds.test, known, seed + 1, constrained)
+    thr, counts, gthr, gcorrect = eng.fit_thresholds(vt, vl)
+    out = {"thresholds": thr, "counts": counts, "global_threshold": gthr, "global_correct": gcorrect}
+    for name, triples, labels, failed in (("valid", vt, vl, vfail), ("test", tt, tl, tfail)):
+        res = classification_accuracy(eng.classify(triples, thr), labels, triples[:, 2], ds.num_relations)
+        res["failed"] = failed
+        out[name] = res
+    return out
