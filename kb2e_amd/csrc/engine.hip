@@ -1792,7 +1792,7 @@ kb2e_status kb2e_take_stats(kb2e_ctx* c, double* loss, int64_t* active) {
             fprintf(stderr, "rpar_cons cycles: setup %llu, P0+rounds %llu, records %llu, longest block %llu, blocks %llu\n",
                     st[3], st[4], st[5], st[6], st[7]);
             if (c->rpar_cons_seq || c->rpar_cons_wide) {
-                unsigned long long q[64];
+                unsigned long long q[96];
                 cons_seq_take_stats(q);
                 fprintf(stderr, "rpar_cons chunk kernel: relations %llu, chunks %llu (most in a relation %llu), "
                         "violators %llu, rounds %llu (most %llu), cycles mean %.0f max %llu\n", q[0], q[1], q[6], q[2],
@@ -1818,6 +1818,11 @@ kb2e_status kb2e_take_stats(kb2e_ctx* c, double* loss, int64_t* active) {
                     fprintf(stderr, "; hot tail:");
                     for (int k = 48; k < 52; ++k) fprintf(stderr, " %llu", q[k]);
                     fprintf(stderr, "; hot cycles %llu", q[43]);
+                    fprintf(stderr, "; hot outside the violator loop (window set-up; B1 wait at 0, 1-2, 3-5, 6+ "
+                            "violators, chunks of each; helper wave 1 after helper_sync without polling: after the walk's "
+                            "end, row staging + P_n loads, corrections + outputs; records on wave 0: W row, slot lists, "
+                            "G loads issue, arrival + staging, record loops):");
+                    for (int k = 52; k < 69; ++k) fprintf(stderr, " %llu", q[k]);
                 }
                 fprintf(stderr, "\n");
             }

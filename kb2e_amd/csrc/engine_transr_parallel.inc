@@ -373,6 +373,14 @@ bool sub_overlap_on() {
     return !(e && e[0] == '0');
 }
 
+// pipelined chain kernel: the steps outside its violator loop (a bit each, of which
+// kPipeOptHandover is kept; default all, KB2E_RPAR_PIPE_OPT=0 the path before them: A/B and
+// the bit comparisons of the tests; read at every batch)
+int32_t pipe_opt_bits() {
+    const char* e = getenv("KB2E_RPAR_PIPE_OPT");
+    return e && e[0] ? (int32_t)(atoi(e) & kPipeOptAll) : kPipeOptAll;
+}
+
 // The kernel arguments of sub-batch j of batch b (the whole batch when c->sub == 1), its
 // exports in buffer set `set`; all but the pair-dedupe tables and the stamp.
 template <typename T>
@@ -445,6 +453,7 @@ void fill_rpar(kb2e_ctx* c, int64_t b, int j, int set, RParArgs& a, RParBufs<T>&
         if (const char* cl = getenv("KB2E_RPAR_CHAIN_LIST")) bf.chain_list = std::max(64, atoi(cl));  // tests
         if (const char* ct = getenv("KB2E_RPAR_CHAIN_TILES")) bf.chain_tiles = std::max(1, atoi(ct));  // tests
         if (const char* rc = getenv("KB2E_RPAR_REC_CAP")) bf.rec_cap = std::max(4, atoi(rc));  // tests
+        bf.pipe_opt = pipe_opt_bits();
     }
     if (c->rpar_cons_wide || c->rpar_cons_gen || c->rpar_widep) {  // the chains past n = 64: pair flags, pre / post split
         bf.pflag = buf_set(set, c->rpar_pflag, c->sb_pflag).as<uint8_t>();

@@ -228,10 +228,17 @@ struct RParBufs {
     int32_t chain_list;  // pipelined chain kernel: pairs a window (0: all that fit the LDS; tests force windows)
     int32_t chain_tiles; // chain kernels: tiles a window (0: the prefix table's 256; tests force windows)
     int32_t rec_cap;     // pipelined chain kernel: records a stage-full of its record pass (0: all that fit the LDS; tests)
+    int32_t pipe_opt;    // pipelined chain kernel: the steps outside its violator loop (KB2E_RPAR_PIPE_OPT bits,
+                         // kPipeOpt*; 0: the path before them.  The same bits on either path)
     int32_t* vio;        // n <= 64 chain kernels: [tiles][kCPairs] the violators' slots of the relation whose
                          // first tile it is (-2: (entity[r], r)); its pair records are made in-kernel
     uint32_t* err;       // pipelined chain: a bounded in-workgroup wait timed out (the host fails loudly)
 };
+
+// RParBufs::pipe_opt (kernels_transr_pipe.hpp), a bit a step outside the chain's violator loop: 2 the chunk
+// hand-over at the barrier (1, the set-up of the prologue and of a window, and 4, the record pass, were
+// measured and dropped: DESIGN.md 7, round 10)
+constexpr int32_t kPipeOptHandover = 2, kPipeOptAll = kPipeOptHandover;
 
 __host__ __device__ constexpr int rm_up16_host_dev(int v) { return (v + 15) & ~15; }
 constexpr int kCPairs = 64;  // transRNorm pairs of a tile (4 St + 1 <= 64)

@@ -36,8 +36,21 @@
 // release store waits on no global store.  The relation's last-update chunk starts
 // after W_c's rows are renormalised: its projections are then made afresh (all
 // waves).  The KB2E_RPAR_STATS counters are a template parameter: the product
-// instantiation has no stamp code.
+// instantiation has no stamp code.  Beside the phases of the walk they stamp what lies
+// outside the violator loop (hot relations, g_seq_stats 52..68): a window's set-up apart
+// from the per-chunk "chunk start", the walker's wait at the chunk barrier B1 by the
+// chunk's violator count, helper wave 1's work between helper_sync and B1 without its
+// polling (row staging, corrections, what follows the walk's end), and the record pass on
+// wave 0 (pipe_records).
+// RParBufs::pipe_opt (KB2E_RPAR_PIPE_OPT, read at every batch; 0: the path before) switches
+// the chunk hand-over step, kPipeOptHandover: the next chunk's rows read once ahead of the
+// helpers' polling, no rewriting of the always-zero |p|^2 partials, the pair flags stored
+// after B1, the helpers' tiles with all their LDS reads ahead of the MFMAs, the debt with two
+// violators' reads in flight.  Loads and stores move; every sum keeps its operands and order,
+// so both paths give the same bits (tests/test_gpu_transr_pipe_outside.py).
 #pragma once
+
+#include <type_traits>
 
 #include "kernels_transr_cons.hpp"  // pair_sum32
 #include "kernels_transr_seq.hpp"
@@ -81,10 +94,13 @@ constexpr int kRecReads = 8;   // 16-byte LDS reads of a staged G row a group (t
 // nslist violator slots are also in LDS (slist, written beside vio during the chain),
 // which saves the hottest relation a round trip to global memory.  bf.rec_cap
 // (tests): fewer records a stage-full, so small relations take several.
-template <typename T, int NP, int L, int STAGE>
+// STATS: wave 0's stamps of the pass into ph[0..4] (thread 0: W_c's row to registers, the
+// slot lists, the issue of the G-row loads, their arrival + the staging stores, the record
+// loops)
+template <typename T, int NP, int L, int STAGE, bool STATS>
 __device__ __forceinline__ void pipe_records(const RParArgs& a, const RParBufs<T>& bf, int r, const int32_t* vio,
                                              int nvt, const T* Wc, T* stage, int* slots, const int* slist,
-                                             int nslist) {
+                                             int nslist, unsigned long long* ph) {
     typedef T T2 __attribute__((ext_vector_type(2)));
     constexpr int NW = kChainThreads / kWave;
     constexpr int CAPW = STAGE / (NW * NP);  // records a wave stages at a time
@@ -93,6 +109,16 @@ __device__ __forceinline__ void pipe_records(const RParArgs& a, const RParBufs<T
     const int n = a.n, ld = a.ld, w = threadIdx.x >> 6, l = lane_id();
     const int nmine = nvt > w ? (nvt - w + NW - 1) / NW : 0;  // records w, w + NW, ...
     if (nmine == 0) return;
+    long long tq = STATS ? clock64() : 0;
+    auto tick = [&](int k) {
+        if constexpr (STATS) {
+            if (threadIdx.x == 0) {
+                const long long t = clock64();
+                ph[k] += (unsigned long long)(t - tq);
+                tq = t;
+            }
+        }
+    };
     const int capw = bf.rec_cap >= NW && bf.rec_cap < NW * CAPW ? bf.rec_cap / NW : CAPW;
     T* gs = stage + w * (CAPW * NP);
     int* sl = slots + w * CAPW;
@@ -107,6 +133,13 @@ __device__ __forceinline__ void pipe_records(const RParArgs& a, const RParBufs<T
             wr[2 * q + 1] = x.y;
         }
     }
+    if constexpr (STATS) {
+        T sink = T(0);  // (the row has arrived)
+#pragma unroll
+        for (int q = 0; q < NP; ++q) sink += wr[q];
+        asm volatile("" ::"v"(sink));
+    }
+    tick(0);
     for (int m0 = 0; m0 < nmine; m0 += capw) {
         const int cnt = nmine - m0 < capw ? nmine - m0 : capw;
         for (int i = l; i < cnt; i += kWave) {
@@ -114,6 +147,7 @@ __device__ __forceinline__ void pipe_records(const RParArgs& a, const RParBufs<T
             sl[i] = k < nslist ? slist[k] : vio[k];
         }
         wave_lds_sync();
+        tick(1);
         for (int i0 = 0; i0 < cnt; i0 += kRecGroup) {
             // the group's slots as wave-uniform values (one LDS read; past the end the last
             // record's again, so the loads and the LDS stores need no branches)
@@ -122,11 +156,17 @@ __device__ __forceinline__ void pipe_records(const RParArgs& a, const RParBufs<T
             T g[kRecGroup];
 #pragma unroll
             for (int u = 0; u < kRecGroup; ++u) g[u] = row_of(__builtin_amdgcn_readlane(sv, u))[l < n ? l : 0];
+            if constexpr (STATS) {
+                __builtin_amdgcn_sched_barrier(0);
+                tick(2);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             if (l < NP) {
 #pragma unroll
                 for (int u = 0; u < kRecGroup; ++u)
                     gs[(i0 + u < cnt ? i0 + u : cnt - 1) * NP + l] = l < n ? g[u] : T(0);
             }
+            tick(3);
         }
         wave_lds_sync();
         // A record's staged row in groups of kRecReads reads, LA groups in flight across
@@ -165,6 +205,7 @@ __device__ __forceinline__ void pipe_records(const RParArgs& a, const RParBufs<T
             if (l < n) row[l] = -(T)a.lr * da;
         }
         wave_lds_sync();  // (every lane has read the staged rows before the next stage-full lands)
+        tick(4);
     }
 }
 
@@ -207,22 +248,32 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     const long long ck0 = STATS ? clock64() : 0;
     int n_chunks = 0;
     unsigned long long n_vio = 0, n_rounds = 0, max_m = 0;
-    __shared__ unsigned long long ph[STATS ? 20 : 1];  // (LDS, not twenty 64-bit registers)
-    if (STATS && threadIdx.x < 20) ph[threadIdx.x] = 0;
-    long long tq = ck0;
+    constexpr int kPh = 40;
+    __shared__ unsigned long long ph[STATS ? kPh : 1];  // (LDS, not forty 64-bit registers)
+    if (STATS && threadIdx.x < kPh) ph[threadIdx.x] = 0;
+    long long tq = ck0, dtq = 0;
     // (phases 12..15 on thread 64, helper wave 1: debt, tiles, helper_sync wait, rows +
     // corrections incl. the wait for the walk's end; 16..19 on thread 0, what follows the
     // chunk loop: a window's last debt + barrier, the helpers' slices to LDS + barrier,
-    // the records, the W write-back)
+    // the records, the W write-back.  20 on thread 0: a window's set-up (tile prefix, list
+    // build, the first row loads, chunk 0 afresh), which phase 1 held before; 21..24 the B1
+    // wait of thread 0 by the chunk's violators (0, 1-2, 3-5, 6+), 25..28 those chunks; 29..31
+    // on thread 64 with a clock of their own, between helper_sync and B1 without the
+    // polling: what follows the walk's end (flags, P_n back, |p|^2), the row staging and
+    // the P_n loads, the violators' corrections and outputs; 32..36 wave 0's record pass,
+    // pipe_records)
     auto tick = [&](int k) {
         if constexpr (STATS) {
             if (threadIdx.x == ((k >= 12 && k < 16) || k == 5 ? 64u : 0u)) {
                 const long long t = clock64();
-                ph[k] += (unsigned long long)(t - tq);
+                dtq = t - tq;
+                ph[k] += (unsigned long long)dtq;
                 tq = t;
             }
         }
     };
+    // the hand-over steps (RParBufs::pipe_opt; wave-uniform)
+    const bool o_hand = (bf.pipe_opt & kPipeOptHandover) != 0;
 
     // W'_r, zero padded to NP x NP
     for (int idx = threadIdx.x; idx < NP * NP; idx += kChainThreads) {
@@ -321,7 +372,10 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
 
     // one 16 x 16 MFMA tile: rows rt of A (Ar) against rows cb of B (a Gram tile);
     // out[(rt 16 + d) * ldo + cb 16 + l16]
-    auto gram_tile = [&](const T* Ar, const T* Bm, int rt, int cb, T* out, int ldo) {
+    // (ahead, a std::bool_constant: every LDS read of the tile in flight before its first MFMA;
+    // left to itself the compiler, short of registers in the walk, reads two k-steps at a time
+    // and waits for each pair.  The MFMAs and their order are the same.)
+    auto gram_tile = [&](const T* Ar, const T* Bm, int rt, int cb, T* out, int ldo, auto ahead) {
         typename M::acc_t acc = {T(0), T(0), T(0), T(0)};
         T av[KS], bv[KS];
 #pragma unroll
@@ -329,18 +383,20 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
             av[s] = Ar[(rt * 16 + l16) * L + 4 * s + kq];
             bv[s] = Bm[(cb * 16 + l16) * L + 4 * s + kq];
         }
+        if constexpr (decltype(ahead)::value) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < KS; ++s) acc = M::mma(av[s], bv[s], acc);
 #pragma unroll
         for (int q = 0; q < 4; ++q) out[(rt * 16 + kq + 4 * q) * ldo + cb * 16 + l16] = acc[q];
     };
     // rows rt of A against the helper's column slice si (its W_c fragments)
-    auto proj_tile = [&](const T* Ar, int rt, int si, T* out) {
+    auto proj_tile = [&](const T* Ar, int rt, int si, T* out, auto ahead) {
         const int cb = hw + 3 * si;
         typename M::acc_t acc = {T(0), T(0), T(0), T(0)};
         T av[KS];
 #pragma unroll
         for (int s = 0; s < KS; ++s) av[s] = Ar[(rt * 16 + l16) * L + 4 * s + kq];
+        if constexpr (decltype(ahead)::value) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < KS; ++s) acc = M::mma(av[s], reg[si * KS + s], acc);
 #pragma unroll
@@ -413,7 +469,7 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     // window's last chunk): the outputs alone.  base: the chunk's first pair in the
     // window lists, cc its pairs.
     auto chunk_outputs = [&](T* Pn, int cn, const T* Pc, const T* An, const T* Ac, const int* vl, int ck, int base,
-                             int cc, int vpar) {
+                             int cc, int vpar, long long t_sync) {
         constexpr int NE = NP / 16, NPS = (R + 11) / 12;
         const int rs = ht >> 4, cb = (ht & 15) * NE;
         T x[NPS][NE];
@@ -423,11 +479,35 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
 #pragma unroll
             for (int u = 0; u < NE; ++u) x[p][u] = j < cn ? Pn[j * L + cb + u] : T(0);
         }
+        // o_hand: the next chunk's rows, the same for every violator, read once ahead of the
+        // polling (they are in place since the chunk before), not once a violator behind its
+        // vl entry: a violator's correction is then one LDS round trip shorter, the last one's
+        // on the walker's path to the barrier
+        T anr[NPS][NE];
+#pragma unroll
+        for (int p = 0; p < NPS; ++p) {
+            const int j = rs + 12 * p;
+#pragma unroll
+            for (int u = 0; u < NE; ++u) anr[p][u] = o_hand && cn > 0 && j < R ? An[j * L + cb + u] : T(0);
+        }
         int used = 0;
+        long long tw = 0;  // (STATS, thread 64: the work between helper_sync and B1, the polling left out)
+        if constexpr (STATS) {
+            if (threadIdx.x == 64u) {
+                T sink = T(0);  // (the P_n loads have arrived)
+#pragma unroll
+                for (int p = 0; p < NPS; ++p)
+#pragma unroll
+                    for (int u = 0; u < NE; ++u) sink += x[p][u];
+                asm volatile("" ::"v"(sink));
+                ph[30] += (unsigned long long)(clock64() - t_sync);
+            }
+        }
         for (uint32_t sp = 0;; ++sp) {
             const bool done = __hip_atomic_load(&misc[6], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == ck;
             const int pw = __hip_atomic_load(&misc[7], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
             const int avail = (pw >> 6) == ck ? (pw & 63) : 0;
+            if constexpr (STATS) tw = clock64();
             for (; used < avail; ++used) {
                 const int v = vl[used];
                 const int slv = ps[base + v];  // the violator's record slot (-2: (entity'[r], r))
@@ -442,8 +522,13 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                     for (int p = 0; p < NPS; ++p) {  // a_{k+1}[j] . a_v, this thread's columns
                         const int j = rs + 12 * p;
                         d[p] = T(0);
+                        if (o_hand) {
 #pragma unroll
-                        for (int u = 0; u < NE; ++u) d[p] = fma(j < R ? An[j * L + cb + u] : T(0), av[u], d[p]);
+                            for (int u = 0; u < NE; ++u) d[p] = fma(anr[p][u], av[u], d[p]);
+                        } else {
+#pragma unroll
+                            for (int u = 0; u < NE; ++u) d[p] = fma(j < R ? An[j * L + cb + u] : T(0), av[u], d[p]);
+                        }
                     }
                     row16_sums<T, NPS>(d);
 #pragma unroll
@@ -467,8 +552,14 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                     }
                 }
             }
+            if constexpr (STATS) {
+                const long long t = clock64();
+                if (threadIdx.x == 64u) ph[31] += (unsigned long long)(t - tw);
+                tw = t;
+            }
             if (done) {
-                if (ht < cc) {
+                // (o_hand: the flags follow the barrier, from the same mask: chunk_flags)
+                if (!o_hand && ht < cc) {
                     const int sl = ps[base + ht];
                     const bool vio_l = ((uint32_t)misc[1 + 2 * vpar] >> ht) & 1;
                     if (sl >= 0) bf.pflag[sl] = vio_l ? 1 : 0;
@@ -482,7 +573,12 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
             }
             __builtin_amdgcn_s_sleep(1);
         }
-        if (cn == 0) return;
+        auto post = [&] {
+            if constexpr (STATS) {
+                if (threadIdx.x == 64u) ph[29] += (unsigned long long)(clock64() - tw);
+            }
+        };
+        if (cn == 0) return post();
         T sq[NPS];
 #pragma unroll
         for (int p = 0; p < NPS; ++p) {
@@ -503,10 +599,24 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                 const int j = rs + 12 * p;
                 if (j < R) {
                     qpart[j] = j < cn ? sq[p] : T(0);
-                    for (int v = 1; v < NB; ++v) qpart[v * R + j] = T(0);
+                    // (o_hand: the other slices' partials are zero since the window's first
+                    // chunk, or the tail, was made afresh -- correct_q -- and nothing else
+                    // writes them)
+                    if (!o_hand)
+                        for (int v = 1; v < NB; ++v) qpart[v * R + j] = T(0);
                 }
             }
         }
+        post();
+    };
+    // o_hand: the chunk's pair flags after the barrier, off the hand-over (the helpers'
+    // first work of the next chunk; vmask: the walker's mask, misc[1 + 2 par])
+    auto chunk_flags = [&](int base, int cc, uint32_t vmask) {
+        if (w == 0 || ht >= cc) return;
+        const int sl = ps[base + ht];
+        const bool vio_l = (vmask >> ht) & 1;
+        if (sl >= 0) bf.pflag[sl] = vio_l ? 1 : 0;
+        else if (vio_l) bf.relpair_stamp[r] = bf.stamp;
     };
     // P_n -= lr C[:, vio] G over the chunk's nv violators (vl; G: their rows of
     // Pc) and the |p_j|^2 partials of the cn rows (qpart[0]; the other slices'
@@ -565,6 +675,42 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
             }
         };
         const int nvu = (bf.dbg & 16) ? 0 : pend_nv;  // (dbg 16, 8: timing experiments)
+        if (o_hand) {
+            // two violators' reads in flight in two register sets of their own (no copies
+            // between them), the slices' G elements read without a lane branch: per
+            // element the same FMAs in the same order
+            T a0[KS], a1[KS], ga[NSW], gb[NSW];
+            auto ld2 = [&](int k, T(&av)[KS], T(&gv)[NSW]) {
+                const int v = __builtin_amdgcn_readlane(vmine, k);
+#pragma unroll
+                for (int s = 0; s < KS; ++s) av[s] = Ap[v * L + 4 * s + kq];
+#pragma unroll
+                for (int si = 0; si < NSW; ++si) {
+                    const int cb = hw + 3 * si;
+                    gv[si] = Pp[v * L + (cb < NB ? cb : 0) * 16 + l16];
+                }
+            };
+            auto fm2 = [&](const T(&av)[KS], const T(&gv)[NSW]) {
+#pragma unroll
+                for (int si = 0; si < NSW; ++si)
+                    if (hw + 3 * si < NB) {
+                        const T gc = -lr * gv[si];
+#pragma unroll
+                        for (int s = 0; s < KS; ++s) reg[si * KS + s] = fma(av[s], gc, reg[si * KS + s]);
+                    }
+            };
+            if (nvu > 0) ld2(0, a0, ga);
+            if (nvu > 1) ld2(1, a1, gb);
+            for (int k = 0; k < nvu; k += 2) {
+                fm2(a0, ga);
+                if (k + 2 < nvu) ld2(k + 2, a0, ga);
+                if (k + 1 < nvu) {
+                    fm2(a1, gb);
+                    if (k + 3 < nvu) ld2(k + 3, a1, gb);
+                }
+            }
+            return;
+        }
         if (nvu > 0) ldv(0);
         for (int k = 0; k < nvu; ++k) {
             T ac[KS], gc[NSW];
@@ -622,9 +768,10 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
 #pragma unroll
             for (int si = 0; si < NSW; ++si)
                 if (hw + 3 * si < NB)
-                    for (int rt = 0; rt < nrt; ++rt) proj_tile(A, rt, si, P);
+                    for (int rt = 0; rt < nrt; ++rt) proj_tile(A, rt, si, P, std::false_type{});
         } else {
-            for (int gi = 0; gi < (nrt == 2 ? 3 : 1); ++gi) gram_tile(A, A, gi == 0 ? 0 : 1, gi == 2 ? 1 : 0, G, LG);
+            for (int gi = 0; gi < (nrt == 2 ? 3 : 1); ++gi)
+                gram_tile(A, A, gi == 0 ? 0 : 1, gi == 2 ? 1 : 0, G, LG, std::false_type{});
         }
         __syncthreads();
         correct_q(P, cc, 0, nullptr, vlist);
@@ -707,6 +854,7 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
             pc = 0;
             fresh(Abuf, e0, Pbuf, Gbuf);
         }
+        tick(20);
         int ka = 0;  // A slot of the current chunk
         for (int base = 0; base < npairs;) {
             const int nbase = chunk_end(base);
@@ -873,7 +1021,10 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
 #pragma unroll
                     for (int si = 0; si < NSW; ++si)
                         if (hw + 3 * si < NB)
-                            for (int rt = 0; rt < nrt; ++rt) proj_tile(An, rt, si, Pn);
+                            for (int rt = 0; rt < nrt; ++rt) {
+                                if (o_hand) proj_tile(An, rt, si, Pn, std::true_type{});
+                                else proj_tile(An, rt, si, Pn, std::false_type{});
+                            }
                     // the Gram tiles to the helpers with the fewest projection tiles (the
                     // same greedy choice on every helper); no cross Gram: chunk_outputs takes
                     // the few violators' dots a_{k+1}[j] . a_v on the fly
@@ -886,7 +1037,10 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
 #pragma unroll
                         for (int h = 1; h < 3; ++h) best = load[h] < load[best] ? h : best;
                         ++load[best];
-                        if (best == hw) gram_tile(An, An, tl == 0 ? 0 : 1, tl == 2 ? 1 : 0, Gn, LG);
+                        if (best == hw) {
+                            if (o_hand) gram_tile(An, An, tl == 0 ? 0 : 1, tl == 2 ? 1 : 0, Gn, LG, std::true_type{});
+                            else gram_tile(An, An, tl == 0 ? 0 : 1, tl == 2 ? 1 : 0, Gn, LG, std::false_type{});
+                        }
                     }
                     (void)crt;
                 }
@@ -895,6 +1049,7 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                 tick(13);
                 helper_sync();
                 tick(14);
+                const long long t_sync = STATS ? clock64() : 0;
                 // chunk k+2's rows into the slot chunk k-1 left, chunk k+3's in flight
                 if (nb2 < npairs || cn > 0) {
                     store_rows(ka == 0 ? 2 : ka - 1);
@@ -903,13 +1058,21 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                 }
                 // chunk k's violators into P_{k+1} as the walker publishes them, then |p|^2;
                 // its records and pair flags to global memory
-                chunk_outputs(Pn, cn, P, An, A, vl, ck, base, cc, par);
+                chunk_outputs(Pn, cn, P, An, A, vl, ck, base, cc, par, t_sync);
                 tick(15);
             }
             __syncthreads();  // B1: the walk, the next chunk's corrected projections and |p|^2
             tick(w == 0 ? 3 : 5);
             const uint32_t vmask = (uint32_t)misc[1 + 2 * par];
             const int nv = misc[2 + 2 * par];
+            if constexpr (STATS) {
+                if (threadIdx.x == 0) {
+                    const int bk = nv == 0 ? 0 : nv <= 2 ? 1 : nv <= 5 ? 2 : 3;
+                    ph[21 + bk] += (unsigned long long)dtq;
+                    ph[25 + bk] += 1;
+                }
+            }
+            if (o_hand) chunk_flags(base, cc, vmask);
             // chunk k's debt passes to the helpers (paid at the next chunk, or below)
             pend_nv = nv;
             pend_par = par;
@@ -955,7 +1118,7 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     // the records first (the A slots, the P buffers and the window lists are free), so
     // that their G row loads queue behind no store; then the matrix to HBM, whole rows
     // by all threads
-    pipe_records<T, NP, L, 5 * R * L>(a, bf, r, vio, nvt, Wc, Abuf, pe, slist, kSlist);
+    pipe_records<T, NP, L, 5 * R * L, STATS>(a, bf, r, vio, nvt, Wc, Abuf, pe, slist, kSlist, ph + (STATS ? 32 : 0));
     if constexpr (STATS) {
         __syncthreads();  // (the slowest wave's records)
         tick(18);
@@ -997,6 +1160,7 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                 atomicAdd(&g_seq_stats[42], n_vio);
                 atomicAdd(&g_seq_stats[43], cyc);
                 for (int k = 0; k < 4; ++k) atomicAdd(&g_seq_stats[48 + k], ph[16 + k]);
+                for (int k = 20; k < 37; ++k) atomicAdd(&g_seq_stats[32 + k], ph[k]);  // 52..68
             }
         }
     }

@@ -50,8 +50,13 @@ constexpr int kSeqMaxTiles = 256;   // tiles of one relation a window (the prefi
 // issue, S3 sums, rows + B2, rounds, shuffles, S5, S6), 24..39 the same over relations of >= 40 chunks,
 // 40 their chunks, 41 their count, 42 their violators; the pipelined kernel (kernels_transr_pipe.hpp, hot: >= 12
 // chunks) also 43 the hot relations' cycles sum, 44..47 what follows the chunk loop (a window's last debt + barrier,
-// the helpers' slices to LDS + barrier, the records, the W write-back), 48..51 the same over the hot relations
-static __device__ unsigned long long g_seq_stats[64];
+// the helpers' slices to LDS + barrier, the records, the W write-back), 48..51 the same over the hot relations; over the hot relations alone 52 a window's set-up (tile
+// prefix, list build, first row loads, chunk 0 afresh: phase "chunk start", 9, no longer holds it), 53..56 the walker's B1
+// wait summed over the chunks of 0, 1-2, 3-5, 6+ violators and 57..60 those chunks, 61..63 helper wave 1 between
+// helper_sync and B1 without its polling (what follows the walk's end; row staging + P_n loads; the violators'
+// corrections and outputs), 64..68 wave 0's record pass (W_c's row to registers, slot lists, issue of the G-row loads,
+// their arrival + staging, the record loops)
+static __device__ unsigned long long g_seq_stats[96];
 
 // sums over the 16 lanes of a DPP row (lanes l & ~15 ... l | 15), in every lane of
 // the row, of K values at once (independent chains, interleaved): the first four

@@ -239,9 +239,9 @@ template void grad_wave_merged_launch<float>(const RParArgs&, const RParBufs<flo
 template void cons_wave_launch<double>(const RParArgs&, const RParBufs<double>&, int, size_t, hipStream_t);
 template void cons_wave_launch<float>(const RParArgs&, const RParBufs<float>&, int, size_t, hipStream_t);
 
-void cons_seq_take_stats(unsigned long long (&st)[64]) {
+void cons_seq_take_stats(unsigned long long (&st)[96]) {
     HIPCHK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_seq_stats), sizeof(st)));
-    unsigned long long z[64] = {};
+    unsigned long long z[96] = {};
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_seq_stats), z, sizeof(z)));
 }
 

@@ -60,7 +60,7 @@ void cons_chaing_launch(const RParArgs& a, const RParBufs<T>& bf, size_t lds, hi
 bool cons_chainw_pipelined(int n);
 // The chunk kernel's counters (relations, chunks, violators, rounds, cycles sum / max,
 // most chunks of a relation), reset.
-void cons_seq_take_stats(unsigned long long (&st)[64]);
+void cons_seq_take_stats(unsigned long long (&st)[96]);
 // Adds the kernel's round statistics (g_rpar_rounds layout) to st and resets them.
 void cons_wave_take_stats(unsigned long long (&st)[16]);
 
