@@ -370,6 +370,51 @@ kb2e_status kb2e_corrupt_triples(kb2e_ctx* ctx, const int32_t* heads, const int3
                                  uint64_t seed, int32_t side, int32_t constrained, int32_t* neg_heads,
                                  int32_t* neg_tails, int64_t* failed);
 
+/* ---- Knowledge-base completion: which facts are missing from the graph?
+ * Query q is the relation relations[q]; its candidates are the triples
+ * (h, t, relations[q]) of every pair of candidate entities, and the answer is
+ * the k most plausible of them that are not known yet (upstream KB2E's
+ * e1_e2.txt, "the top-500 entity pairs which are calculated by TransE", is
+ * such a list).  The call follows the contract of "Using a trained model"
+ * above: read-only (tables, training state, glibc stream and TransR work
+ * vectors stay), stateless FP64 energies with transr_compat ignored, FP32
+ * tables widened first, every model, distance, precision and dim, every device
+ * buffer freed before return (also on the error paths), a stream
+ * synchronisation at the end.
+ *   Candidates.  constrained = 0: every h and every t in 0..|E|-1.
+ *   constrained = 1: h from the head pool of the relation and t from its tail
+ *   pool, the distinct entities seen in that slot of that relation among the
+ *   `known` triples (kb2e_corrupt_triples' pools); a relation with an empty
+ *   pool has no candidates.
+ *   Exclusions.  A candidate listed among the `known` triples, and with
+ *   exclude_loops = 1 every candidate with h == t.  Nothing else; nknown == 0
+ *   with NULL arrays is legal.
+ *   Energy.  What kb2e_score_triples gives the same triple, bit for bit: the
+ *   evaluator's (P_r(t) - P_r(h)) - r_k, one serial FP64 sum over k from zero.
+ *   Output.  Per query the found[q] = min(k, candidates - excluded) remaining
+ *   candidates of smallest energy in ascending (energy, head id, tail id) order
+ *   in heads[q*k + j], tails[q*k + j], energy[q*k + j]; slots at and after
+ *   found[q] hold -1, -1 and +inf.  1 <= k <= 1024 (k may exceed the candidate
+ *   count).  A relation may be listed more than once; each listing is answered.
+ * The |E|^2 keys of a relation are never held.  Besides the projection table
+ * [dim][|E|] and the set of known triples, the call's device memory is a record
+ * buffer of fixed capacity, 256 MiB whatever |E| is
+ * (KB2E_COMPLETE_BUFFER_BYTES=<bytes> lowers it, for tests): the heads are
+ * walked in strips whose candidates fit the buffer -- the first strip is 16
+ * heads, KB2E_COMPLETE_STRIP_HEADS=<n> caps the later ones (tests) -- and a
+ * candidate becomes a record only if its energy is at most the k-th best so far
+ * and it is neither an excluded loop nor known; after each strip the k best
+ * are selected on the device on (energy, head id, tail id).  The result does
+ * not depend on the launch geometry, the strip size, the buffer size or the
+ * order in which the records were appended.
+ * KB2E_EINVAL: nrel < 1, k out of range, a flag other than 0 / 1, an id out of
+ * range in `relations` or in `known`, a NULL array with a count > 0. */
+kb2e_status kb2e_complete_triples(kb2e_ctx* ctx, const int32_t* relations, int64_t nrel, int32_t k,
+                                  const int32_t* known_heads, const int32_t* known_tails,
+                                  const int32_t* known_relations, int64_t nknown, int32_t constrained,
+                                  int32_t exclude_loops, int32_t* heads /* [nrel][k] */, int32_t* tails /* [nrel][k] */,
+                                  double* energy /* [nrel][k] */, int64_t* found /* [nrel] */);
+
 /* Raw glibc stream access (the context's RNG, as std::rand() in the reference). */
 int32_t kb2e_rng_next(kb2e_ctx* ctx);
 
@@ -381,7 +426,8 @@ int32_t kb2e_rng_next(kb2e_ctx* ctx);
  * "relpred_select", "relpred_rank"; kb2e_fit_thresholds / kb2e_classify_triples:
  * "classify_score" (energies, and the comparison of kb2e_classify_triples),
  * "classify_sort" (every radix pass), "classify_fit" (segment starts and both
- * sweeps); kb2e_corrupt_triples: "classify_corrupt").  Returns total
+ * sweeps); kb2e_corrupt_triples: "classify_corrupt"; kb2e_complete_triples:
+ * "complete_score" (projection + the tile kernel), "complete_select").  Returns total
  * milliseconds and launch count since kb2e_profile_enable.  on = 0: off;
  * on = P >= 1: the batch kernels of every P-th batch are timed (event records
  * cost device time of their own; sampling keeps the rest of the run unperturbed),
@@ -394,7 +440,11 @@ kb2e_status kb2e_profile_query(kb2e_ctx* ctx, const char* name, double* total_ms
  * context's stream.  Names: "transh_orth_rel_batches" -- PARALLEL TransH batches
  * whose normOrth relation pass ran (the gate on the previous batch's normOrth
  * work, kernels_transh_parallel.hpp); the other batches took the one-wave pass
- * alone.  KB2E_EINVAL for an unknown name. */
+ * alone.  Of the last kb2e_complete_triples call (kept on the host):
+ * "complete_candidates" -- pairs scored, "complete_records" -- records
+ * appended, "complete_strips" -- score + select steps,
+ * "complete_buffer_records" -- the record buffer's capacity in records.
+ * KB2E_EINVAL for an unknown name. */
 kb2e_status kb2e_counter(kb2e_ctx* ctx, const char* name, int64_t* value);
 
 /* Device memory the context holds, in bytes: every device buffer it has allocated

@@ -30,6 +30,7 @@
 #include "eval.hpp"
 #include "predict.hpp"
 #include "classify.hpp"
+#include "complete.hpp"
 #include "host_data.hpp"
 #include "kernels_common.hpp"
 #include "kernels_index.hpp"
@@ -174,6 +175,7 @@ struct kb2e_ctx {
     DevBuf hpar_tag;                       // PARALLEL TransH: per entity, the relations its flagged pairs have
     uint32_t hpar_stamp = 0;
     DevBuf hpar_clk;                       // KB2E_HPAR_CLK: the w-apply workgroups' clocks (diagnostic)
+    CompleteStats complete_stats;  // kb2e_complete_triples: the last call's counters (kb2e_counter)
     DevBuf hpar_count;                     // PARALLEL TransH: normOrth iterations of the last two batches, relation passes run
     uint32_t hpar_orth_min = 0;            // ... from which normOrth takes the relation pass
     int32_t hpar_orth_q = 0;               // the one-wave pass's second-sweep queue (kOrthQ)
@@ -2040,6 +2042,24 @@ kb2e_status kb2e_corrupt_triples(kb2e_ctx* c, const int32_t* heads, const int32_
     });
 }
 
+kb2e_status kb2e_complete_triples(kb2e_ctx* c, const int32_t* relations, int64_t nrel, int32_t k, const int32_t* kh,
+                                  const int32_t* kt, const int32_t* kr, int64_t nknown, int32_t constrained,
+                                  int32_t exclude_loops, int32_t* heads, int32_t* tails, double* energy,
+                                  int64_t* found) {
+    return guarded(c, [&] {
+        if (!relations || nrel < 1 || !heads || !tails || !energy || !found || nknown < 0 ||
+            (nknown > 0 && (!kh || !kt || !kr)))
+            return fail(c, KB2E_EINVAL, "no relations to complete");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        c->complete_stats = CompleteStats{};
+        complete_triples(eval_tables(c), CompleteQuery{relations, nrel, k, kh, kt, kr, nknown, constrained, exclude_loops},
+                         heads, tails, energy, found, &c->complete_stats, &hooks);
+        return KB2E_OK;
+    });
+}
+
 int32_t kb2e_rng_next(kb2e_ctx* c) {
     if (!c) return -1;
     c->rng_version++;
@@ -2070,6 +2090,13 @@ kb2e_status kb2e_profile_query(kb2e_ctx* c, const char* name, double* total_ms, 
 kb2e_status kb2e_counter(kb2e_ctx* c, const char* name, int64_t* value) {
     return guarded(c, [&] {
         const std::string nm = name ? name : "";
+        if (value && nm.rfind("complete_", 0) == 0) {  // kb2e_complete_triples: the last call (host-side numbers)
+            const CompleteStats& cs = c->complete_stats;
+            if (nm == "complete_candidates") return *value = cs.candidates, KB2E_OK;
+            if (nm == "complete_records") return *value = cs.records, KB2E_OK;
+            if (nm == "complete_strips") return *value = cs.strips, KB2E_OK;
+            if (nm == "complete_buffer_records") return *value = cs.buffer_records, KB2E_OK;
+        }
         if (nm != "transh_orth_rel_batches" || !value) return fail(c, KB2E_EINVAL, "unknown counter '" + nm + "'");
         *value = 0;
         if (!c->hpar_count.p) return KB2E_OK;  // (not a PARALLEL TransH context, or no triples yet)

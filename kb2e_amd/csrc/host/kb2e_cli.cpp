@@ -4,7 +4,9 @@
 // top-k answers to (h, ?, r) / (?, t, r) entity queries and (h, t, ?) relation
 // queries from the trained tables; --queries FILE, --topk K, --filtered 0|1)
 // and classifyTransE / classifyTransH / classifyTransR (triple classification:
-// thresholds fitted on the valid split, accuracy on the test split).
+// thresholds fitted on the valid split, accuracy on the test split) and
+// completeTransE / completeTransH / completeTransR (knowledge-base completion:
+// the top-k new triples of each relation).
 //
 // Same flags, defaults, stdout lines and files as the reference binaries
 // (transe/bin/trainTransE.cpp, common/args.cpp, common/loader.cpp,
@@ -125,6 +127,10 @@ void printUsage(const char* invoked) {  // common/args.cpp:125-142
     printf("   --validlabels FILE (classifyTrans*: head<TAB>tail<TAB>relation<TAB>label lines, 1 / -1 or 0; instead of generated negatives)\n");
     printf("   --testlabels FILE (classifyTrans*: likewise for the test split)\n");
     printf("   --out FILE (classifyTrans*: label<TAB>energy of every classified test triple)\n");
+    printf("   --relations FILE (completeTrans*: relation names, one per line; every relation without it)\n");
+    printf("   --topk [10] --constrained [1] (completeTrans*: heads / tails from the entities seen in that slot of the relation)\n");
+    printf("   --loops [0] (completeTrans*: 1 = head == tail may be an answer)\n");
+    printf("   --filtered [1] (completeTrans*: known = train + valid + test; 0 = train + valid)\n");
 }
 
 EmbeddingArguments parseArgs(int argc, char** argv) {  // common/args.cpp:53-122
@@ -751,6 +757,76 @@ int classify_main(int argc, char** argv, kb2e_model model) {
     return 0;
 }
 
+// completeTransE|H|R: knowledge-base completion of the tables evalTrans* loads
+// (kb2e_complete_triples): per relation the --topk K [10] most plausible
+// triples that are not known.  --relations FILE names the relations, one per
+// line (unknown names are reported and skipped, in the loader's wording);
+// without it every relation is mined.  --constrained 0|1 [1: heads and tails
+// from the entities seen in that slot of the relation among the known triples],
+// --loops 0|1 [0: head == tail is no answer], --filtered 0|1 [1: known = train +
+// valid + test; 0: train + valid, so that test triples can be found].  One line
+// per answer: relation name, position (from 1), head name, tail name, energy.
+int complete_main(int argc, char** argv, kb2e_model model) {
+    EmbeddingArguments args = parseArgs(argc, argv);
+    printf("%s\n", args.to_string().c_str());
+    int i, topk = 10, constrained = 1, loops = 0, filtered = 1;
+    std::string relFile;
+    if ((i = argpos("relations", true, argc, argv)) != -1) relFile = argv[i + 1];
+    if ((i = argpos("topk", true, argc, argv)) != -1) topk = atoi(argv[i + 1]);
+    if ((i = argpos("constrained", true, argc, argv)) != -1) constrained = atoi(argv[i + 1]) ? 1 : 0;
+    if ((i = argpos("loops", true, argc, argv)) != -1) loops = atoi(argv[i + 1]) ? 1 : 0;
+    if ((i = argpos("filtered", true, argc, argv)) != -1) filtered = atoi(argv[i + 1]);
+    FILE* f = nullptr;
+    if (!relFile.empty() && !(f = fopen(relFile.c_str(), "r"))) {
+        printf("Could not open relation file: %s\n", relFile.c_str());
+        exit(2);
+    }
+    LoadedModel L;
+    load_model(args, model, L);
+    const int nr = (int)L.relation2id.size();
+    std::vector<std::string> names(L.entity2id.size()), rnames((size_t)nr);
+    for (const auto& kv : L.entity2id)
+        if (kv.second >= 0 && (size_t)kv.second < names.size()) names[(size_t)kv.second] = kv.first;
+    for (const auto& kv : L.relation2id)
+        if (kv.second >= 0 && kv.second < nr) rnames[(size_t)kv.second] = kv.first;
+    std::vector<int32_t> rels;
+    if (f) {
+        char rb[512];
+        while (fscanf(f, "%511s", rb) == 1) {
+            if (!L.relation2id.count(rb)) {
+                std::cout << "Relation found in triple file that was not found in the identity file: " << rb << std::endl;
+                continue;
+            }
+            rels.push_back(L.relation2id[rb]);
+        }
+        fclose(f);
+    } else {
+        for (int r = 0; r < nr; ++r) rels.push_back(r);
+    }
+    if (rels.empty()) {
+        printf("No relations to complete\n");
+        exit(1);
+    }
+    // load_model lists the test triples first: without them the rest is train + valid
+    const size_t skip = filtered ? 0 : L.th.size();
+    const int64_t nknown = (int64_t)(L.fh.size() - skip);
+    const int32_t *kh = nknown ? L.fh.data() + skip : nullptr, *kt = nknown ? L.ft.data() + skip : nullptr,
+                  *kr = nknown ? L.fr.data() + skip : nullptr;
+    const size_t nq = rels.size(), k = (size_t)std::max(topk, 1);
+    std::vector<int32_t> heads(nq * k), tails(nq * k);
+    std::vector<double> energy(nq * k);
+    std::vector<int64_t> found(nq);
+    check(L.ctx, kb2e_complete_triples(L.ctx, rels.data(), (int64_t)nq, topk, kh, kt, kr, nknown, constrained,
+                                       loops ? 0 : 1, heads.data(), tails.data(), energy.data(), found.data()),
+          "complete_triples");
+    for (size_t q = 0; q < nq; ++q)
+        for (int64_t j = 0; j < found[q]; ++j)
+            printf("%s\t%lld\t%s\t%s\t%.6lf\n", rnames[(size_t)rels[q]].c_str(), (long long)(j + 1),
+                   names[(size_t)heads[q * k + j]].c_str(), names[(size_t)tails[q * k + j]].c_str(), energy[q * k + j]);
+    kb2e_destroy(L.ctx);
+    return 0;
+}
+
 }  // namespace kb2e_host
 
 #ifndef KB2E_CLI_NO_MAIN  // (tests/native/host_check.cpp includes this file for its parser and loader)
@@ -771,7 +847,11 @@ int main(int argc, char** argv) {
     if (prog == "classifyTransE") return classify_main(argc, argv, KB2E_TRANSE);
     if (prog == "classifyTransH") return classify_main(argc, argv, KB2E_TRANSH);
     if (prog == "classifyTransR") return classify_main(argc, argv, KB2E_TRANSR);
-    fprintf(stderr, "invoke as trainTransE|H|R, evalTransE|H|R, predictTransE|H|R or classifyTransE|H|R (got %s)\n",
+    if (prog == "completeTransE") return complete_main(argc, argv, KB2E_TRANSE);
+    if (prog == "completeTransH") return complete_main(argc, argv, KB2E_TRANSH);
+    if (prog == "completeTransR") return complete_main(argc, argv, KB2E_TRANSR);
+    fprintf(stderr,
+            "invoke as trainTransE|H|R, evalTransE|H|R, predictTransE|H|R, classifyTransE|H|R or completeTransE|H|R (got %s)\n",
             prog.c_str());
     return 2;
 }

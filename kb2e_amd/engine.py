@@ -30,7 +30,7 @@ EXPORTS = [
     "kb2e_read_table", "kb2e_comm_unique_id", "kb2e_comm_init_rank", "kb2e_comm_init_group", "kb2e_merge_epoch",
     "kb2e_merge_epoch_group", "kb2e_comm_info", "kb2e_get_config", "kb2e_score_triples", "kb2e_predict",
     "kb2e_rank_triples", "kb2e_predict_relations", "kb2e_rank_relations", "kb2e_fit_thresholds",
-    "kb2e_classify_triples", "kb2e_corrupt_triples",
+    "kb2e_classify_triples", "kb2e_corrupt_triples", "kb2e_complete_triples",
 ]
 COMM_ID_BYTES = 128
 READ_VERBATIM, READ_UNIT, READ_SHRINK = 0, 1, 2
@@ -100,6 +100,8 @@ def lib():
             "kb2e_classify_triples": (i32, [vp, i32p, i32p, i32p, i64, dp, u8p, dp]),
             "kb2e_corrupt_triples": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, C.c_uint64, i32, i32,
                                            i32p, i32p, C.POINTER(i64)]),
+            "kb2e_complete_triples": (i32, [vp, i32p, i64, i32, i32p, i32p, i32p, i64, i32, i32, i32p, i32p, dp,
+                                            C.POINTER(i64)]),
             "kb2e_comm_unique_id": (i32, [u8p]),
             "kb2e_comm_init_rank": (i32, [vp, i32, i32, u8p]),
             "kb2e_comm_init_group": (i32, [C.POINTER(vp), i32]),
@@ -495,6 +497,32 @@ class Engine:
                                                C.c_uint64(int(seed) & (2 ** 64 - 1)), int(side), int(bool(constrained)),
                                                _ip(nh), _ip(nt), C.byref(failed)), "corrupt_triples")
         return np.stack([nh, nt, cols[2]], axis=1), failed.value
+
+    # ------------------------------------------------ knowledge-base completion
+    def complete(self, relations, k, known=None, constrained=False, exclude_loops=False):
+        """The k most plausible new triples of each listed relation: the candidates
+        of relations[q] are the triples (h, t, relations[q]) of every entity pair
+        (constrained: h from the relation's head pool, t from its tail pool, the
+        entities seen in that slot among the rows of `known`); rows of `known` are
+        excluded, and with exclude_loops the pairs h == t.  Returns (heads
+        int32[nrel, k], tails int32[nrel, k], energy float64[nrel, k], found
+        int64[nrel]): ascending (energy, head, tail), energies are score()'s bits,
+        padded with -1 / -1 / +inf after found[q]."""
+        r = np.ascontiguousarray(relations, dtype=np.int32).reshape(-1)
+        nrel, k = len(r), int(k)
+        for name, flag in (("constrained", constrained), ("exclude_loops", exclude_loops)):
+            if flag not in (0, 1, False, True):
+                raise EngineError(f"complete_triples: EINVAL: {name} must be 0 or 1")
+        kc, nk = self._filter_cols(known)
+        kk = max(k, 1)
+        heads = np.full((nrel, kk), -1, np.int32)
+        tails = np.full((nrel, kk), -1, np.int32)
+        en = np.full((nrel, kk), np.inf)
+        found = np.zeros(nrel, np.int64)
+        self._check(lib().kb2e_complete_triples(self.h, _ip(r), nrel, k, *[None if c is None else _ip(c) for c in kc], nk,
+                                                int(constrained), int(exclude_loops), _ip(heads), _ip(tails), _dp(en),
+                                                found.ctypes.data_as(C.POINTER(C.c_int64))), "complete_triples")
+        return heads, tails, en, found
 
     def device_bytes(self):
         return lib().kb2e_device_bytes(self.h)

@@ -23,7 +23,9 @@ evaluation task of those papers (Socher et al. 2013; TransH 4.3, TransR 4.3):
 per-relation energy thresholds fitted on the validation split
 (``Engine.fit_thresholds``), negatives generated on the device where the data
 set ships none (``Engine.corrupt``), accuracy on the test split
-(``Engine.classify``).
+(``Engine.classify``).  ``completion`` is the hold-out measure of knowledge-base
+completion: the k most plausible new triples of each relation mined on the
+device (``Engine.complete``) against the relation's test triples.
 """
 from __future__ import annotations
 
@@ -225,3 +227,55 @@ def triple_classification(eng, ds, *, seed=0, constrained=True, valid=None, test
         res["failed"] = failed
         out[name] = res
     return out
+
+
+def completion_metrics(heads, tails, found, relations, test, known, k):
+    """Recall@k and precision@k of ``Engine.complete`` output (one row per entry
+    of `relations`) against the hold-out triples `test`: per relation the number
+    of its test triples -- distinct, and not among the rows of `known`, which the
+    mining excludes -- that are among the mined pairs.  recall = hits / test
+    triples (None without one), precision = hits / mined (None when nothing was
+    mined).  Returns {"k", "relations", "mined", "test", "hits", "recall",
+    "precision", "per_relation": {r: {"mined", "test", "hits", "recall",
+    "precision"}}}; a relation listed twice is counted once."""
+    heads, tails = np.asarray(heads), np.asarray(tails)
+    found = np.asarray(found).reshape(-1)
+    relations = np.asarray(relations).reshape(-1)
+    test = np.asarray(test, dtype=np.int64).reshape(-1, 3)
+    known = np.asarray(known, dtype=np.int64).reshape(-1, 3)
+    hold = {}
+    for h, t, r in test.tolist():
+        hold.setdefault(r, set()).add((h, t))
+    for h, t, r in known.tolist():
+        if r in hold:
+            hold[r].discard((h, t))
+    per = {}
+    for q, r in enumerate(relations.tolist()):
+        if r in per:
+            continue
+        nf = int(found[q])
+        mined = set(zip(heads[q, :nf].tolist(), tails[q, :nf].tolist()))
+        truth = hold.get(r, set())
+        hits = len(mined & truth)
+        per[int(r)] = {"mined": nf, "test": len(truth), "hits": hits,
+                       "recall": hits / len(truth) if truth else None,
+                       "precision": hits / nf if nf else None}
+    mined = sum(v["mined"] for v in per.values())
+    ntest = sum(v["test"] for v in per.values())
+    hits = sum(v["hits"] for v in per.values())
+    return {"k": int(k), "relations": len(per), "mined": mined, "test": ntest, "hits": hits,
+            "recall": hits / ntest if ntest else None, "precision": hits / mined if mined else None,
+            "per_relation": per}
+
+
+def completion(eng, ds, k, *, constrained=True, exclude_loops=True, relations=None):
+    """Knowledge-base completion with a hold-out: the k most plausible new triples
+    of each relation (every relation unless `relations` lists some) are mined on
+    the device with known = train + valid (``Engine.complete``), and the
+    relation's test triples are looked up among them: recall@k and precision@k
+    per relation and overall (``completion_metrics``)."""
+    known = np.concatenate([ds.train, ds.valid]).astype(np.int32)
+    rels = np.arange(ds.num_relations, dtype=np.int32) if relations is None else \
+        np.ascontiguousarray(relations, dtype=np.int32).reshape(-1)
+    heads, tails, _, found = eng.complete(rels, k, known, constrained=constrained, exclude_loops=exclude_loops)
+    return completion_metrics(heads, tails, found, rels, ds.test, known, k)
