@@ -1823,8 +1823,10 @@ kb2e_status kb2e_take_stats(kb2e_ctx* c, double* loss, int64_t* active) {
                     fprintf(stderr, "; hot outside the violator loop (window set-up; B1 wait at 0, 1-2, 3-5, 6+ "
                             "violators, chunks of each; helper wave 1 after helper_sync without polling: after the walk's "
                             "end, row staging + P_n loads, corrections + outputs; records on wave 0: W row, slot lists, "
-                            "G loads issue, arrival + staging, record loops):");
-                    for (int k = 52; k < 69; ++k) fprintf(stderr, " %llu", q[k]);
+                            "G loads issue, arrival + staging, record loops; helper wave 1 from a violator's publish to "
+                            "the end of its correction, those violators):");
+                    for (int k = 52; k < 71; ++k) fprintf(stderr, " %llu", q[k]);
+                    fprintf(stderr, "; relations with deferred records %llu, their records %llu", q[71], q[72]);
                 }
                 fprintf(stderr, "\n");
             }

@@ -144,7 +144,7 @@ void setup_transr_parallel(kb2e_ctx* c) {
     c->rpar_tile_act.alloc((size_t)(nkeys + 1) * 4);
     c->rpar_pair.alloc((size_t)c->B * 4 * c->ld * es);
     c->rpar_relpair.alloc((size_t)g.num_relations * c->ld * es);
-    c->rpar_relpair_stamp.alloc((size_t)g.num_relations * 4);
+    c->rpar_relpair_stamp.alloc((size_t)g.num_relations * 4 * 2);  // (then RParBufs::rec_stamp, [R])
     memset_sync(c->rpar_relpair_stamp.p, 0, c->rpar_relpair_stamp.bytes);
     c->rpar_tiles.alloc((size_t)(nkeys + 1) * sizeof(RTile));
     c->rpar_ntiles.alloc((size_t)(nkeys + 1) * 4);
@@ -373,12 +373,20 @@ bool sub_overlap_on() {
     return !(e && e[0] == '0');
 }
 
-// pipelined chain kernel: the steps outside its violator loop (a bit each, of which
-// kPipeOptHandover is kept; default all, KB2E_RPAR_PIPE_OPT=0 the path before them: A/B and
+// pipelined chain kernel: the steps outside its violator loop (a bit each: kPipeOptHandover,
+// kPipeOptDefer, kPipeOptPublish; default all, KB2E_RPAR_PIPE_OPT=0 the path before them: A/B and
 // the bit comparisons of the tests; read at every batch)
 int32_t pipe_opt_bits() {
     const char* e = getenv("KB2E_RPAR_PIPE_OPT");
     return e && e[0] ? (int32_t)(atoi(e) & kPipeOptAll) : kPipeOptAll;
+}
+
+// kPipeOptDefer: the chunks from which a relation defers its records (KB2E_RPAR_REC_DEFER; 0: none
+// does, 1: every relation with a pair, tests; the results do not depend on it; read at every batch)
+constexpr int32_t kRecDeferChunks = 12;  // (swept 4 / 8 / 12 / 16 on the bench: DESIGN.md 7, round 11)
+int32_t rec_defer_chunks() {
+    const char* e = getenv("KB2E_RPAR_REC_DEFER");
+    return e && e[0] ? std::max(0, atoi(e)) : kRecDeferChunks;
 }
 
 // The kernel arguments of sub-batch j of batch b (the whole batch when c->sub == 1), its
@@ -454,6 +462,10 @@ void fill_rpar(kb2e_ctx* c, int64_t b, int j, int set, RParArgs& a, RParBufs<T>&
         if (const char* ct = getenv("KB2E_RPAR_CHAIN_TILES")) bf.chain_tiles = std::max(1, atoi(ct));  // tests
         if (const char* rc = getenv("KB2E_RPAR_REC_CAP")) bf.rec_cap = std::max(4, atoi(rc));  // tests
         bf.pipe_opt = pipe_opt_bits();
+        if (c->rpar_cons_seq) {  // the pipelined chain: long relations leave their records to the entity pass
+            bf.rec_stamp = bf.relpair_stamp + c->cfg.num_relations;
+            bf.rec_defer = rec_defer_chunks();
+        }
     }
     if (c->rpar_cons_wide || c->rpar_cons_gen || c->rpar_widep) {  // the chains past n = 64: pair flags, pre / post split
         bf.pflag = buf_set(set, c->rpar_pflag, c->sb_pflag).as<uint8_t>();

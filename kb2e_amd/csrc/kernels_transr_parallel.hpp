@@ -233,12 +233,19 @@ struct RParBufs {
     int32_t* vio;        // n <= 64 chain kernels: [tiles][kCPairs] the violators' slots of the relation whose
                          // first tile it is (-2: (entity[r], r)); its pair records are made in-kernel
     uint32_t* err;       // pipelined chain: a bounded in-workgroup wait timed out (the host fails loudly)
+    uint32_t* rec_stamp; // [R] batch stamp when the relation's pair records (bf.pair, bf.relpair) are still the
+                         // G rows this launch: the entity pass converts them (rpar_record_convert).  Null on
+                         // every path but the pipelined chain's
+    int32_t rec_defer;   // pipelined chain kernel: a relation of this many chunks or more defers its records
+                         // (KB2E_RPAR_REC_DEFER; 0: none, 1: every relation with a pair)
 };
 
 // RParBufs::pipe_opt (kernels_transr_pipe.hpp), a bit a step outside the chain's violator loop: 2 the chunk
-// hand-over at the barrier (1, the set-up of the prologue and of a window, and 4, the record pass, were
+// hand-over at the barrier, 8 the long relations' records deferred to the entity pass, 16 a violator published
+// ahead of the later rows' update (1, the set-up of the prologue and of a window, and 4, the record pass, were
 // measured and dropped: DESIGN.md 7, round 10)
-constexpr int32_t kPipeOptHandover = 2, kPipeOptAll = kPipeOptHandover;
+constexpr int32_t kPipeOptHandover = 2, kPipeOptDefer = 8, kPipeOptPublish = 16;
+constexpr int32_t kPipeOptAll = kPipeOptHandover | kPipeOptDefer | kPipeOptPublish;
 
 __host__ __device__ constexpr int rm_up16_host_dev(int v) { return (v + 15) & ~15; }
 constexpr int kCPairs = 64;  // transRNorm pairs of a tile (4 St + 1 <= 64)
@@ -838,6 +845,44 @@ __global__ __launch_bounds__(256) void transr_constraint_kernel(RParArgs a, RPar
 // touches the row as head or tail, pre otherwise).
 constexpr int kRParWaves = 16;
 
+// A deferred pair record of the pipelined chain (kernels_transr_pipe.hpp, kPipeOptDefer): the relation
+// carries this launch's stamp in bf.rec_stamp, its rows of bf.pair / bf.relpair still hold the violators' G,
+// and da = -lr W G with the relation's final matrix (bf.W, written by the chain launch before this one) is
+// made here, by the wave that adds the record.  v: the G row as lane_pair_load left it (elements 2l, 2l + 1,
+// zero past n) -> da in the same layout.  n <= 64, the pipelined chain's widths: lane j < n takes row j of
+// the matrix, streamed from L2 in 16-byte loads (ld is even, so rows are 16-byte aligned), kRecSteps steps
+// of four columns in flight; G's elements are wave-uniform values read from the lanes that hold them.  The
+// sum is pipe_records': acc[i & 3] = fma(W[j][i], G[i], acc[i & 3]) for i ascending, (acc0 + acc1) + (acc2 +
+// acc3), times -lr.  pipe_records also adds the padded terms n <= i < NP, fma(+-0, +0, acc).  They are exact
+// no-ops: a chain that starts at +0 never holds -0 (under round-to-nearest a sum is -0 only if both addends
+// are, and the first addend of every step is the chain), and x + (+-0) = x for every x but -0; the columns past
+// n of the last step here are such terms too (W's element replaced by +0, G's lanes past n hold +0).
+constexpr int kRecSteps = 4;
+template <typename T>
+__device__ __forceinline__ void rpar_record_convert(const RParArgs& a, const RParBufs<T>& bf, int r, T (&v)[2]) {
+    typedef T T2 __attribute__((ext_vector_type(2)));
+    const int n = a.n, l = lane_id();
+    const T2* wrow = (const T2*)(bf.W + ((int64_t)r * n + (l < n ? l : 0)) * a.ld);
+    const int nq = (n + 1) >> 1;  // 16-byte pairs of a row
+    T acc[4] = {T(0), T(0), T(0), T(0)};
+    for (int q0 = 0; 2 * q0 < n; q0 += 2 * kRecSteps) {
+        T2 x[2 * kRecSteps];
+#pragma unroll
+        for (int q = 0; q < 2 * kRecSteps; ++q) x[q] = wrow[q0 + q < nq ? q0 + q : nq - 1];
+#pragma unroll
+        for (int q = 0; q < 2 * kRecSteps; ++q) {
+            const int i = 2 * (q0 + q);  // columns i, i + 1: G's in lane i / 2 (q0 is even: i & 3 = 2 q & 3)
+            const T g0 = readlane_f(v[0], (q0 + q) & (kWave - 1)), g1 = readlane_f(v[1], (q0 + q) & (kWave - 1));
+            acc[(2 * q) & 3] = fma(i < n ? x[q].x : T(0), g0, acc[(2 * q) & 3]);
+            acc[(2 * q + 1) & 3] = fma(i + 1 < n ? x[q].y : T(0), g1, acc[(2 * q + 1) & 3]);
+        }
+    }
+    const T da = -(T)a.lr * ((acc[0] + acc[1]) + (acc[2] + acc[3]));  // lane j: element j
+    const T d0 = __shfl(da, (2 * l) & (kWave - 1)), d1 = __shfl(da, (2 * l + 1) & (kWave - 1));
+    v[0] = 2 * l < n ? d0 : T(0);
+    v[1] = 2 * l + 1 < n ? d1 : T(0);
+}
+
 // The row's last active update in the batch, kk 2 + u (-1: none), over the
 // events [p0 + 64 first, ...) of its segment in strides of 64 stride; the
 // maximum in every lane.
@@ -869,10 +914,12 @@ __device__ __forceinline__ void rpar_entity_events(const RParArgs& a, const RPar
                                                    bool& dirty, bool& dirty2, bool& er_seen) {
     const int n = a.n, ld = a.ld, l = lane_id();
     const bool split = !GRAD && bf.last_renorm;
+    const bool defer = !GRAD && bf.rec_stamp != nullptr;  // (wave-uniform: only the pipelined chain defers records)
     for (int base = p0 + first * kWave; base < p1; base += stride * kWave) {
         const int p = base + l;
         int src = -1;     // row of the y / pair table this lane's event adds (GRAD: its y row)
         int src2 = -1;    // !GRAD: second pair row (the row is head and tail of the update)
+        int rdef = -1;    // !GRAD: the event's relation when its records are deferred (rpar_record_convert)
         T c = T(0);
         bool nrm = false, er = false, post = false;
         if (p < p1) {
@@ -900,6 +947,10 @@ __device__ __forceinline__ void rpar_entity_events(const RParArgs& a, const RPar
                         if (src < 0) src = s0 + 1;
                         else src2 = s0 + 1;
                     }
+                    if (defer && src >= 0) {
+                        const int r = a.rels[a.si[kk]];
+                        if (bf.rec_stamp[r] == bf.stamp) rdef = r;
+                    }
                 }
             }
         }
@@ -922,6 +973,14 @@ __device__ __forceinline__ void rpar_entity_events(const RParArgs& a, const RPar
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                     if (q < k) lane_pair_load(tab + (int64_t)readlane_i32(mine, ev[q]) * ld, n, v[q]);
+                if (defer && __ballot(rdef >= 0)) {  // deferred records: G -> da, before they are added
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        if (q < k) {
+                            const int rq = readlane_i32(rdef, ev[q]);
+                            if (rq >= 0) rpar_record_convert<T>(a, bf, rq, v[q]);
+                        }
+                }
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                     if (q < k) {
@@ -943,6 +1002,7 @@ __device__ __forceinline__ void rpar_entity_finish(const RParArgs& a, const RPar
     if (!GRAD && er_seen && row < a.nr && bf.relpair_stamp[row] == bf.stamp) {
         T dv[2];
         lane_pair_load(bf.relpair + (int64_t)row * ld, n, dv);
+        if (bf.rec_stamp && bf.rec_stamp[row] == bf.stamp) rpar_record_convert<T>(a, bf, row, dv);  // deferred: G -> da
         if (split && last < 0) {  // no update renormalises the row: the delta stays
             acc2[0] += dv[0];
             acc2[1] += dv[1];

@@ -46,8 +46,14 @@
 // the chunk hand-over step, kPipeOptHandover: the next chunk's rows read once ahead of the
 // helpers' polling, no rewriting of the always-zero |p|^2 partials, the pair flags stored
 // after B1, the helpers' tiles with all their LDS reads ahead of the MFMAs, the debt with two
-// violators' reads in flight.  Loads and stores move; every sum keeps its operands and order,
-// so both paths give the same bits (tests/test_gpu_transr_pipe_outside.py).
+// violators' reads in flight; kPipeOptDefer: a relation of bf.rec_defer chunks or more runs no
+// record pass -- its G rows stay in the record tables under the relation's stamp (bf.rec_stamp)
+// and the entity pass, the next launch, makes da from them on the waves that add it
+// (rpar_record_convert, kernels_transr_parallel.hpp: the hottest relation's ~100 records no longer
+// queue on four waves behind its chain); kPipeOptPublish: the walker publishes a violator right
+// behind its G row, ahead of the later rows' update, so the helpers' correction runs under that
+// update.  Loads and stores move; every sum keeps its operands and order, so all paths give the
+// same bits (tests/test_gpu_transr_pipe_outside.py, tests/test_gpu_transr_pipe_defer.py).
 #pragma once
 
 #include <type_traits>
@@ -251,6 +257,7 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     constexpr int kPh = 40;
     __shared__ unsigned long long ph[STATS ? kPh : 1];  // (LDS, not forty 64-bit registers)
     if (STATS && threadIdx.x < kPh) ph[threadIdx.x] = 0;
+    __shared__ long long pubt[STATS ? kChainRows : 1];  // (STATS: thread 0's clock at a violator's publish)
     long long tq = ck0, dtq = 0;
     // (phases 12..15 on thread 64, helper wave 1: debt, tiles, helper_sync wait, rows +
     // corrections incl. the wait for the walk's end; 16..19 on thread 0, what follows the
@@ -261,7 +268,8 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     // on thread 64 with a clock of their own, between helper_sync and B1 without the
     // polling: what follows the walk's end (flags, P_n back, |p|^2), the row staging and
     // the P_n loads, the violators' corrections and outputs; 32..36 wave 0's record pass,
-    // pipe_records)
+    // pipe_records; 37, 38 on thread 64: from the walker's publish of a violator to the end of
+    // its correction, and those violators)
     auto tick = [&](int k) {
         if constexpr (STATS) {
             if (threadIdx.x == ((k >= 12 && k < 16) || k == 5 ? 64u : 0u)) {
@@ -274,6 +282,8 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     };
     // the hand-over steps (RParBufs::pipe_opt; wave-uniform)
     const bool o_hand = (bf.pipe_opt & kPipeOptHandover) != 0;
+    const bool o_defer = (bf.pipe_opt & kPipeOptDefer) != 0 && bf.rec_stamp != nullptr;
+    const bool o_pub = (bf.pipe_opt & kPipeOptPublish) != 0;
 
     // W'_r, zero padded to NP x NP
     for (int idx = threadIdx.x; idx < NP * NP; idx += kChainThreads) {
@@ -283,13 +293,18 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     // the relation's run of tiles, its last active sample's tile and how many of
     // that tile's pairs belong to the sample's corrupted-triple update (the tail)
     if (w == 0) {
-        int run = 0;
+        int run = 0, npt = 0;  // (npt: the run's pairs, this lane's tiles; o_defer alone reads them)
         for (int m0 = 0;; m0 += kWave) {
             const int g = g0 + m0 + l;
             const uint64_t b = __ballot(t0 + g < t1 && a.td_r[t0 + g] == r);
             const int k = b == ~0ull ? kWave : __builtin_ctzll(~b);
+            if (o_defer && l < k) npt += bf.cnrows[g] & 127;
             run += k;
             if (k < kWave) break;
+        }
+        if (o_defer) {
+#pragma unroll
+            for (int s = 32; s >= 1; s >>= 1) npt += __shfl_xor(npt, s);
         }
         const int c0 = bf.cnrows[g0] & 127;
         const int rel = c0 > 0 && bf.cpairs[(int64_t)g0 * 2 * kCPairs + kCPairs + c0 - 1] == -2;
@@ -314,10 +329,14 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
             misc[4] = gt;
             misc[5] = run;
             misc[6] = ntail;
+            misc[7] = npt;
         }
     }
     __syncthreads();
     const int run = misc[5], has_rel = misc[3], g_tail = misc[4], n_tail = misc[6];
+    // o_defer: a relation of bf.rec_defer chunks or more (of R pairs; the tail's chunk of its own is not
+    // counted) leaves its records to the entity pass -- see the tail below
+    const bool defer = o_defer && bf.rec_defer > 0 && (misc[7] + kChainRows - 1) / kChainRows >= bf.rec_defer;
     // K0 = W'^T W' (four waves, MFMA) into the P buffers; wave 0 keeps column l of it,
     // the helper waves their slices of W' (the working matrix) -- in the same registers
     T reg[4 * KS];
@@ -549,6 +568,12 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                     if (ht == 0) {
                         vio[nvt + used] = slv;
                         if (nvt + used < kSlist) slist[nvt + used] = slv;
+                    }
+                }
+                if constexpr (STATS) {  // from the walker's publish of the violator to the end of its correction
+                    if (threadIdx.x == 64u) {
+                        ph[37] += (unsigned long long)(clock64() - pubt[used]);
+                        ph[38] += 1;
                     }
                 }
             }
@@ -967,6 +992,20 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                         // its vio slot are the helper waves', chunk_outputs)
                         if (c < NP) P[v * L + c] = g;
                         tick(10);
+                        // o_pub: v is published here, right behind its G row's store and ahead of the later
+                        // rows' update, which no reader of the publish word needs (chunk_outputs reads the G
+                        // row, A's row v, the vl entry and the slot): the helpers correct v while the later
+                        // rows move, and the last violator's correction is off the walker's way to B1.  (The
+                        // release waits for the G row's store before the later rows' reads of it are issued.
+                        // With the publish between those reads and their FMAs instead, so that the two waits
+                        // coincide, the kernel took 53 more AGPRs and 260 more v_accvgpr moves under the
+                        // lanes' branch and was slower on the bench than this order: DESIGN.md 7, round 11.)
+                        if (o_pub && l == 0) {
+                            vl[npub] = v;
+                            if constexpr (STATS) pubt[npub] = clock64();
+                            __hip_atomic_store(&misc[7], (ck << 6) | (npub + 1), __ATOMIC_RELEASE,
+                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
                         const bool upd = j > v && j < cc;
                         T qh = T(0);  // this lane's half of |p_j|^2
                         if (upd) {
@@ -992,8 +1031,9 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                             if (upd) q = tot;
                         }
                         // publish v to the helper waves: its G row (above) and vl entry first
-                        if (l == 0) {
+                        if (!o_pub && l == 0) {
                             vl[npub] = v;
+                            if constexpr (STATS) pubt[npub] = clock64();
                             __hip_atomic_store(&misc[7], (ck << 6) | (npub + 1), __ATOMIC_RELEASE,
                                                __HIP_MEMORY_SCOPE_WORKGROUP);
                         }
@@ -1118,7 +1158,12 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
     // the records first (the A slots, the P buffers and the window lists are free), so
     // that their G row loads queue behind no store; then the matrix to HBM, whole rows
     // by all threads
-    pipe_records<T, NP, L, 5 * R * L, STATS>(a, bf, r, vio, nvt, Wc, Abuf, pe, slist, kSlist, ph + (STATS ? 32 : 0));
+    // o_defer, a long relation: no record pass behind its chain.  Its violators' rows of bf.pair / bf.relpair
+    // keep the G rows chunk_outputs wrote, the relation carries this launch's stamp, and the entity pass makes
+    // da = -lr W G from the matrix written back below (rpar_record_convert: the same sum), on the waves that
+    // add the records, all over the GPU instead of on this workgroup's four
+    if (!defer) pipe_records<T, NP, L, 5 * R * L, STATS>(a, bf, r, vio, nvt, Wc, Abuf, pe, slist, kSlist, ph + (STATS ? 32 : 0));
+    else if (threadIdx.x == 0 && nvt > 0) bf.rec_stamp[r] = bf.stamp;
     if constexpr (STATS) {
         __syncthreads();  // (the slowest wave's records)
         tick(18);
@@ -1160,7 +1205,11 @@ __global__ __launch_bounds__(kChainThreads) void transr_cons_pipe_kernel(RParArg
                 atomicAdd(&g_seq_stats[42], n_vio);
                 atomicAdd(&g_seq_stats[43], cyc);
                 for (int k = 0; k < 4; ++k) atomicAdd(&g_seq_stats[48 + k], ph[16 + k]);
-                for (int k = 20; k < 37; ++k) atomicAdd(&g_seq_stats[32 + k], ph[k]);  // 52..68
+                for (int k = 20; k < 39; ++k) atomicAdd(&g_seq_stats[32 + k], ph[k]);  // 52..70
+            }
+            if (defer && nvt > 0) {
+                atomicAdd(&g_seq_stats[71], 1ull);
+                atomicAdd(&g_seq_stats[72], (unsigned long long)nvt);
             }
         }
     }

@@ -55,7 +55,9 @@ constexpr int kSeqMaxTiles = 256;   // tiles of one relation a window (the prefi
 // wait summed over the chunks of 0, 1-2, 3-5, 6+ violators and 57..60 those chunks, 61..63 helper wave 1 between
 // helper_sync and B1 without its polling (what follows the walk's end; row staging + P_n loads; the violators'
 // corrections and outputs), 64..68 wave 0's record pass (W_c's row to registers, slot lists, issue of the G-row loads,
-// their arrival + staging, the record loops)
+// their arrival + staging, the record loops), 69 helper wave 1 from the walker's publish of a violator to the end of
+// its correction and 70 those violators; over all relations 71 those that deferred their records to the entity pass
+// (RParBufs::rec_stamp) and 72 their records
 static __device__ unsigned long long g_seq_stats[96];
 
 // sums over the 16 lanes of a DPP row (lanes l & ~15 ... l | 15), in every lane of
