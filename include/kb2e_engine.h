@@ -415,6 +415,86 @@ kb2e_status kb2e_complete_triples(kb2e_ctx* ctx, const int32_t* relations, int64
                                   int32_t exclude_loops, int32_t* heads /* [nrel][k] */, int32_t* tails /* [nrel][k] */,
                                   double* energy /* [nrel][k] */, int64_t* found /* [nrel] */);
 
+/* ---- Entity fold-in: give new entities a row without retraining.  The free
+ * entities' rows of the device entity table are learnt from example triples
+ * while everything else is frozen: every other entity row, the relation and
+ * weight tables, the training state, the glibc stream, the TransR work vectors
+ * and kb2e_device_bytes are the same, bit for bit, before and after, and
+ * training may continue afterwards.  Every model, distance, precision and dim a
+ * context takes.  The call synchronises the stream first and last.
+ *   Context values: width n, learning rate lr, margin g, distance (L1 / L2;
+ *   TransH always L1).  A free entity f has a working row x in FP64; FP32 tables
+ *   are widened on load and a free row is rounded to FP32 once, when it is
+ *   stored at the end.  Every example holds exactly one free entity, as head or
+ *   as tail.  For each free entity the call runs `epochs` passes over its
+ *   examples in the caller's order; the free entities do not interact, and the
+ *   result depends neither on their order nor on the launch geometry.  For pass
+ *   p and example i (its index in the caller's arrays), triple (h, t, r):
+ *   1. Slot: side 0 corrupts the head, 1 the tail, 2 a fair coin (the
+ *      reference's unif): the top bit of u(p, i, 0), 1 = tail.  The stream is
+ *      kb2e_corrupt_triples' SplitMix64, stateless (the glibc stream is not
+ *      touched):  state = mix(seed),
+ *                 u(p, i, a) = mix(state + ((p * count + i) << 7) + a).
+ *   2. Negative: for draws a = 1..32, e = u(p, i, a) % |E|; a draw is rejected
+ *      if e is a free entity (any of them), if e is the entity it replaces, or
+ *      if the new triple is among the `known` triples or the examples.  The
+ *      first accepted draw gives the corrupted triple; without one the sample is
+ *      skipped and counted as failed.  (So no row is read that the call writes.)
+ *   3. Energies E+ and E- of the two triples: kb2e_score_triples' stateless
+ *      formulas with x as the row of f (TransR from zeroed work vectors;
+ *      transr_compat is ignored); sums over the row are 64-lane reductions.
+ *   4. Hinge: unless E+ + g > E- the sample is done.  Otherwise
+ *      loss_p += g + E+ - E- and the sample counts as active.
+ *   5. Update, y = x first; then the positive triple with b = -1 and the
+ *      corrupted triple with b = +1, skipping a triple that does not hold f (the
+ *      corrupted one, when f's own slot was replaced).  Every gradient is taken
+ *      at x, the row before this sample (the reference's snapshot rule for a
+ *      batch of one sample).  Per triple:
+ *      TransE (transe/trainer.cpp:28-45): g_k = 2 (t_k - h_k - r_k), under L1
+ *        then 1 if g_k > 0 and -1 otherwise; f the head: y_k -= b lr g_k, f the
+ *        tail: y_k += b lr g_k; then norm(y), which scales to unit length only
+ *        if |y| > 1.
+ *      TransH (transh/trainer.cpp:14-37): hs = w.h, ts = w.t, g_k the L1 sign of
+ *        2 ((t_k - ts w_k) - (h_k - hs w_k) - r_k); y and norm(y) as TransE;
+ *        then, against the stored w: while w.y > 0.1, y -= lr w.
+ *      TransR (transr/trainer.cpp:147-176): hp_k = sum_j W[j][k] h_j, tp_k
+ *        likewise, g_k = 2 (tp_k - hp_k - r_k) with the L1 sign as above; f the
+ *        head: y_j -= b lr g_k W[j][k] for k ascending (f the tail: +=); then y
+ *        is scaled to unit length (always); then, against the stored W with
+ *        q = yW: while sum_k q_k^2 > 1, y_j -= lr sum_k 2 q_k W[j][k].  That
+ *        loop is the gradient step of |yW|^2, the simultaneous form of the
+ *        reference's transRNorm with the matrix held fixed; it differs from the
+ *        reference's in-place column sweep by O(lr^2) -- deliberately: W is
+ *        frozen here, and a sweep costs two dependent wave steps instead of n.
+ *      A coupling loop makes at most max_sweeps steps (0 means 10000); one that
+ *      still fails its test then stops with the row as it stands and counts as
+ *      capped.  The cap is a safety bound, not a tuning knob.
+ *   6. x = y.
+ *   For TransE this is the reference's prebatch; train_kb; postbatch on a
+ *   one-sample batch with every row but f's put back afterwards, and the same
+ *   holds for TransH and TransR whenever neither coupling loop fires.
+ * rows_in [nfree][dim] gives the rows to start from (NULL: the rows as they
+ * stand in the table); rows_out [nfree][dim] (may be NULL) receives the rows as
+ * stored; loss[f*2 + 0..1] = the first and the last pass's loss of free entity
+ * f; counts[f*3 + 0..2] = its active, failed and capped counts over all passes.
+ * A free entity without examples is legal: its row is rows_in's or unchanged
+ * and its loss is 0.  nknown == 0 and count == 0 with NULL arrays are legal.
+ * One wave owns one free entity for all passes, its row in registers; TransR
+ * stages the sample's matrix in LDS up to n = 141 and reads it from L2 above
+ * (KB2E_FOLD_W_L2=1 forces that; KB2E_FOLD_GRID=<n> caps the workgroups: tests).
+ * KB2E_EINVAL: nfree < 1, epochs < 1, a side other than 0 / 1 / 2,
+ * max_sweeps < 0, an id out of range, a free id listed twice, an example with
+ * no free entity or with a free entity in both slots (the same one or two
+ * different ones), a NULL array with a count > 0.  KB2E_ESTATE: no embeddings
+ * on the device.  Folding in new relations is not offered. */
+kb2e_status kb2e_fold_in_entities(kb2e_ctx* ctx, const int32_t* free_entities, int64_t nfree,
+                                  const int32_t* heads, const int32_t* tails, const int32_t* relations, int64_t count,
+                                  const int32_t* known_heads, const int32_t* known_tails,
+                                  const int32_t* known_relations, int64_t nknown, int32_t epochs, uint64_t seed,
+                                  int32_t side, int32_t max_sweeps, const double* rows_in /* [nfree][dim] or NULL */,
+                                  double* rows_out /* [nfree][dim] or NULL */, double* loss /* [nfree][2] */,
+                                  int64_t* counts /* [nfree][3] */);
+
 /* Raw glibc stream access (the context's RNG, as std::rand() in the reference). */
 int32_t kb2e_rng_next(kb2e_ctx* ctx);
 
@@ -427,7 +507,8 @@ int32_t kb2e_rng_next(kb2e_ctx* ctx);
  * "classify_score" (energies, and the comparison of kb2e_classify_triples),
  * "classify_sort" (every radix pass), "classify_fit" (segment starts and both
  * sweeps); kb2e_corrupt_triples: "classify_corrupt"; kb2e_complete_triples:
- * "complete_score" (projection + the tile kernel), "complete_select").  Returns total
+ * "complete_score" (projection + the tile kernel), "complete_select";
+ * kb2e_fold_in_entities: "foldin").  Returns total
  * milliseconds and launch count since kb2e_profile_enable.  on = 0: off;
  * on = P >= 1: the batch kernels of every P-th batch are timed (event records
  * cost device time of their own; sampling keeps the rest of the run unperturbed),

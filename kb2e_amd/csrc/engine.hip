@@ -31,6 +31,7 @@
 #include "predict.hpp"
 #include "classify.hpp"
 #include "complete.hpp"
+#include "foldin.hpp"
 #include "host_data.hpp"
 #include "kernels_common.hpp"
 #include "kernels_index.hpp"
@@ -2058,6 +2059,26 @@ kb2e_status kb2e_complete_triples(kb2e_ctx* c, const int32_t* relations, int64_t
         c->complete_stats = CompleteStats{};
         complete_triples(eval_tables(c), CompleteQuery{relations, nrel, k, kh, kt, kr, nknown, constrained, exclude_loops},
                          heads, tails, energy, found, &c->complete_stats, &hooks);
+        return KB2E_OK;
+    });
+}
+
+kb2e_status kb2e_fold_in_entities(kb2e_ctx* c, const int32_t* free_entities, int64_t nfree, const int32_t* heads,
+                                  const int32_t* tails, const int32_t* relations, int64_t count, const int32_t* kh,
+                                  const int32_t* kt, const int32_t* kr, int64_t nknown, int32_t epochs, uint64_t seed,
+                                  int32_t side, int32_t max_sweeps, const double* rows_in, double* rows_out,
+                                  double* loss, int64_t* counts) {
+    return guarded(c, [&] {
+        if (!free_entities || nfree < 1 || !loss || !counts || count < 0 || nknown < 0 ||
+            (count > 0 && (!heads || !tails || !relations)) || (nknown > 0 && (!kh || !kt || !kr)))
+            return fail(c, KB2E_EINVAL, "no free entities, or a NULL array with a count > 0");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        fold_in_entities(eval_tables(c),
+                         FoldQuery{free_entities, nfree, heads, tails, relations, count, kh, kt, kr, nknown, epochs, seed,
+                                   side, max_sweeps, c->cfg.learning_rate, c->cfg.margin, rows_in},
+                         rows_out, loss, counts, &hooks);
         return KB2E_OK;
     });
 }

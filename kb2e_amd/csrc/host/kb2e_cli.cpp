@@ -6,7 +6,9 @@
 // and classifyTransE / classifyTransH / classifyTransR (triple classification:
 // thresholds fitted on the valid split, accuracy on the test split) and
 // completeTransE / completeTransH / completeTransR (knowledge-base completion:
-// the top-k new triples of each relation).
+// the top-k new triples of each relation) and foldinTransE / foldinTransH /
+// foldinTransR (entity fold-in: rows for new entities with the trained tables
+// frozen).
 //
 // Same flags, defaults, stdout lines and files as the reference binaries
 // (transe/bin/trainTransE.cpp, common/args.cpp, common/loader.cpp,
@@ -131,6 +133,8 @@ void printUsage(const char* invoked) {  // common/args.cpp:125-142
     printf("   --topk [10] --constrained [1] (completeTrans*: heads / tails from the entities seen in that slot of the relation)\n");
     printf("   --loops [0] (completeTrans*: 1 = head == tail may be an answer)\n");
     printf("   --filtered [1] (completeTrans*: known = train + valid + test; 0 = train + valid)\n");
+    printf("   --new FILE --foldout DIR (foldinTrans*: triples that mention the new entities; where the full entity table goes)\n");
+    printf("   --epochs [1000] --seed [now] --side [2] (foldinTrans*: passes, seed of the new rows and of the negatives, slot to corrupt)\n");
 }
 
 EmbeddingArguments parseArgs(int argc, char** argv) {  // common/args.cpp:53-122
@@ -827,6 +831,136 @@ int complete_main(int argc, char** argv, kb2e_model model) {
     return 0;
 }
 
+// foldinTransE|H|R: rows for entities the model was not trained on
+// (kb2e_fold_in_entities).  --datadir D holds entity2id.txt with the old
+// entities first and the new ones after them; the tables in --outdir O have rows
+// for the old entities only.  --new FILE lists the triples that mention the new
+// entities (exactly one new entity each), --foldout DIR receives the full
+// entity2vec.<method>: the old entities' lines byte for byte as they are in O,
+// then one line per new entity.  A new row starts as kb2e_init_params draws it
+// for --seed; known = train + valid + test + FILE.  Pass p is one call with
+// seed --seed + p (its negatives differ from pass to pass and its summed loss is
+// printed: "Pass: p, Loss: x").
+int foldin_main(int argc, char** argv, kb2e_model model) {
+    EmbeddingArguments args = parseArgs(argc, argv);
+    printf("%s\n", args.to_string().c_str());
+    int i, side = 2;
+    std::string newFile, foldOut;
+    if ((i = argpos("new", true, argc, argv)) != -1) newFile = argv[i + 1];
+    if ((i = argpos("foldout", true, argc, argv)) != -1) foldOut = argv[i + 1];
+    if ((i = argpos("side", true, argc, argv)) != -1) side = atoi(argv[i + 1]);
+    if (newFile.empty() || foldOut.empty()) {
+        printf("Argument missing for %s\n", newFile.empty() ? "new" : "foldout");
+        exit(1);
+    }
+    const std::string m = method_name(args.method);
+    const std::string relPath = args.outputDir + "/relation2vec." + m, entPath = args.outputDir + "/entity2vec." + m,
+                      wPath = args.outputDir + "/weights." + m;
+    std::map<std::string, int> entity2id, relation2id;
+    loadIdFile(args.dataDir + "/entity2id.txt", entity2id);
+    loadIdFile(args.dataDir + "/relation2id.txt", relation2id);
+    const int ne = (int)entity2id.size(), nr = (int)relation2id.size(), n = args.embeddingSize;
+    // the old entity table: its lines are kept as they are
+    std::vector<std::string> lines;
+    {
+        FILE* f = fopen(entPath.c_str(), "r");
+        if (!f) {
+            printf("Could not find entity embedding file: %s. Make sure to specify the path and/or train.\n", entPath.c_str());
+            exit(2);
+        }
+        std::string line;
+        int ch;
+        while ((ch = fgetc(f)) != EOF) {
+            line.push_back((char)ch);
+            if (ch == '\n') {
+                lines.push_back(line);
+                line.clear();
+            }
+        }
+        fclose(f);
+    }
+    const int neOld = (int)lines.size();
+    if (neOld < 1 || neOld >= ne) {
+        printf("%s has %d rows and entity2id.txt %d entities: no new entity\n", entPath.c_str(), neOld, ne);
+        exit(1);
+    }
+    kb2e_config cfg;
+    kb2e_default_config(&cfg);
+    cfg.model = model;
+    cfg.dim = n;
+    cfg.num_entities = ne;
+    cfg.num_relations = nr;
+    cfg.learning_rate = args.learningRate;
+    cfg.margin = args.margin;
+    cfg.method = args.method;
+    cfg.distance = args.distanceType;
+    cfg.seed = args.seed;
+    cfg.precision = 64;
+    cfg.device = args.device;
+    kb2e_ctx* ctx = nullptr;
+    check(nullptr, kb2e_create(&cfg, &ctx), "create");
+    const size_t wn = model == KB2E_TRANSE ? 0 : model == KB2E_TRANSH ? (size_t)nr * n : (size_t)nr * n * n;
+    std::vector<double> E((size_t)ne * n), R((size_t)nr * n), W(wn);
+    check(ctx, kb2e_init_params(ctx, E.data(), R.data(), wn ? W.data() : nullptr), "init_params");  // the new rows
+    for (int e = 0; e < neOld; ++e) {
+        const char* p = lines[(size_t)e].c_str();
+        for (int k = 0; k < n; ++k) {
+            char* end = nullptr;
+            E[(size_t)e * n + k] = strtod(p, &end);
+            if (end == p) {
+                printf("Failed to read embedding values from file: '%s'\n", entPath.c_str());
+                exit(1);
+            }
+            p = end;
+        }
+    }
+    if (kb2e_read_table(ctx, 1, relPath.c_str(), KB2E_READ_VERBATIM) != KB2E_OK) {
+        printf("Failed to read embedding values from file: '%s'\n", relPath.c_str());
+        exit(1);
+    }
+    if (wn && kb2e_read_table(ctx, 2, wPath.c_str(), KB2E_READ_VERBATIM) != KB2E_OK) {
+        printf("Failed to read embedding weight values from seed file: '%s'\n", wPath.c_str());
+        exit(1);
+    }
+    check(ctx, kb2e_download_params(ctx, nullptr, R.data(), wn ? W.data() : nullptr), "download_params");
+    check(ctx, kb2e_upload_params(ctx, E.data(), R.data(), wn ? W.data() : nullptr), "upload_params");
+
+    std::vector<int32_t> xh, xt, xr, kh, kt, kr;
+    auto addKnown = [&](int h, int t, int r) { kh.push_back(h); kt.push_back(t); kr.push_back(r); };
+    loadTripleFile(newFile, entity2id, relation2id, [&](int h, int t, int r) {
+        xh.push_back(h); xt.push_back(t); xr.push_back(r); addKnown(h, t, r); });
+    for (const char* split : {"/train.txt", "/valid.txt", "/test.txt"})
+        loadTripleFile(args.dataDir + split, entity2id, relation2id, addKnown);
+    std::vector<int32_t> free((size_t)(ne - neOld));
+    for (int e = neOld; e < ne; ++e) free[(size_t)(e - neOld)] = e;
+    std::vector<double> rows(free.size() * (size_t)n), loss(free.size() * 2);
+    std::vector<int64_t> counts(free.size() * 3);
+    for (int p = 0; p < args.maxEpochs; ++p) {
+        check(ctx, kb2e_fold_in_entities(ctx, free.data(), (int64_t)free.size(), xh.data(), xt.data(), xr.data(),
+                                         (int64_t)xh.size(), kh.data(), kt.data(), kr.data(), (int64_t)kh.size(), 1,
+                                         (uint64_t)args.seed + (uint64_t)p, side, 0, nullptr, rows.data(), loss.data(),
+                                         counts.data()), "fold_in_entities");
+        double sum = 0;
+        for (size_t f = 0; f < free.size(); ++f) sum += loss[f * 2];
+        printf("Pass: %d, Loss: %f\n", p, sum);
+        fflush(stdout);
+    }
+    const std::string outPath = foldOut + "/entity2vec." + m;
+    FILE* out = fopen(outPath.c_str(), "w");
+    if (!out) {
+        printf("Could not open output file: %s\n", outPath.c_str());
+        exit(1);
+    }
+    for (const std::string& line : lines) fwrite(line.data(), 1, line.size(), out);
+    for (size_t f = 0; f < free.size(); ++f) {  // common/trainer.cpp:109-127
+        for (int k = 0; k < n; ++k) fprintf(out, "%.6lf\t", rows[f * n + k]);
+        fprintf(out, "\n");
+    }
+    fclose(out);
+    kb2e_destroy(ctx);
+    return 0;
+}
+
 }  // namespace kb2e_host
 
 #ifndef KB2E_CLI_NO_MAIN  // (tests/native/host_check.cpp includes this file for its parser and loader)
@@ -850,8 +984,12 @@ int main(int argc, char** argv) {
     if (prog == "completeTransE") return complete_main(argc, argv, KB2E_TRANSE);
     if (prog == "completeTransH") return complete_main(argc, argv, KB2E_TRANSH);
     if (prog == "completeTransR") return complete_main(argc, argv, KB2E_TRANSR);
+    if (prog == "foldinTransE") return foldin_main(argc, argv, KB2E_TRANSE);
+    if (prog == "foldinTransH") return foldin_main(argc, argv, KB2E_TRANSH);
+    if (prog == "foldinTransR") return foldin_main(argc, argv, KB2E_TRANSR);
     fprintf(stderr,
-            "invoke as trainTransE|H|R, evalTransE|H|R, predictTransE|H|R, classifyTransE|H|R or completeTransE|H|R (got %s)\n",
+            "invoke as trainTransE|H|R, evalTransE|H|R, predictTransE|H|R, classifyTransE|H|R, completeTransE|H|R or "
+            "foldinTransE|H|R (got %s)\n",
             prog.c_str());
     return 2;
 }

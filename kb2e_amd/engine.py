@@ -30,7 +30,7 @@ EXPORTS = [
     "kb2e_read_table", "kb2e_comm_unique_id", "kb2e_comm_init_rank", "kb2e_comm_init_group", "kb2e_merge_epoch",
     "kb2e_merge_epoch_group", "kb2e_comm_info", "kb2e_get_config", "kb2e_score_triples", "kb2e_predict",
     "kb2e_rank_triples", "kb2e_predict_relations", "kb2e_rank_relations", "kb2e_fit_thresholds",
-    "kb2e_classify_triples", "kb2e_corrupt_triples", "kb2e_complete_triples",
+    "kb2e_classify_triples", "kb2e_corrupt_triples", "kb2e_complete_triples", "kb2e_fold_in_entities",
 ]
 COMM_ID_BYTES = 128
 READ_VERBATIM, READ_UNIT, READ_SHRINK = 0, 1, 2
@@ -102,6 +102,8 @@ def lib():
                                            i32p, i32p, C.POINTER(i64)]),
             "kb2e_complete_triples": (i32, [vp, i32p, i64, i32, i32p, i32p, i32p, i64, i32, i32, i32p, i32p, dp,
                                             C.POINTER(i64)]),
+            "kb2e_fold_in_entities": (i32, [vp, i32p, i64, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, i32, C.c_uint64,
+                                            i32, i32, dp, dp, dp, C.POINTER(i64)]),
             "kb2e_comm_unique_id": (i32, [u8p]),
             "kb2e_comm_init_rank": (i32, [vp, i32, i32, u8p]),
             "kb2e_comm_init_group": (i32, [C.POINTER(vp), i32]),
@@ -523,6 +525,39 @@ class Engine:
                                                 int(constrained), int(exclude_loops), _ip(heads), _ip(tails), _dp(en),
                                                 found.ctypes.data_as(C.POINTER(C.c_int64))), "complete_triples")
         return heads, tails, en, found
+
+    # ------------------------------------------------ entity fold-in
+    def fold_in(self, free, examples, known=None, *, epochs, seed=0, side=2, max_sweeps=0, rows=None):
+        """Learn the rows of the `free` entities from the (head, tail, relation)
+        rows of `examples`, each of which holds exactly one free entity, with every
+        other row, relation vector, normal and matrix frozen: `epochs` passes of
+        margin-ranking SGD per free entity over its examples in the given order,
+        negatives drawn per sample (side 0 head, 1 tail, 2 a coin) from the
+        entities that are neither free nor make a row of `known` or `examples`.
+        `rows` float64[nfree, dim] are the rows to start from (None: as they stand
+        in the table); max_sweeps caps the coupling loops (0: 10000).  Only the
+        free rows of the device entity table change.  Returns (rows
+        float64[nfree, dim] as stored, loss float64[nfree, 2] = first and last
+        pass, counts int64[nfree, 3] = active, failed, capped); the step is
+        spelled out in include/kb2e_engine.h (kb2e_fold_in_entities)."""
+        f = np.ascontiguousarray(free, dtype=np.int32).reshape(-1)
+        ex = np.ascontiguousarray(examples, dtype=np.int32).reshape(-1, 3)
+        ec = [np.ascontiguousarray(ex[:, k]) for k in range(3)]
+        kc, nk = self._filter_cols(known)
+        rin = None
+        if rows is not None:
+            rin = np.ascontiguousarray(rows, dtype=np.float64)
+            if rin.shape != (len(f), self.n):
+                raise ValueError(f"rows must be [{len(f)}, {self.n}]")
+        out = np.zeros((len(f), self.n))
+        loss = np.zeros((len(f), 2))
+        counts = np.zeros((len(f), 3), np.int64)
+        self._check(lib().kb2e_fold_in_entities(self.h, _ip(f), len(f), *[_ip(c) if len(ex) else None for c in ec],
+                                                len(ex), *[None if c is None else _ip(c) for c in kc], nk, int(epochs),
+                                                C.c_uint64(int(seed) & (2 ** 64 - 1)), int(side), int(max_sweeps),
+                                                _dp(rin), _dp(out), _dp(loss),
+                                                counts.ctypes.data_as(C.POINTER(C.c_int64))), "fold_in_entities")
+        return out, loss, counts
 
     def device_bytes(self):
         return lib().kb2e_device_bytes(self.h)

@@ -26,6 +26,9 @@ set ships none (``Engine.corrupt``), accuracy on the test split
 (``Engine.classify``).  ``completion`` is the hold-out measure of knowledge-base
 completion: the k most plausible new triples of each relation mined on the
 device (``Engine.complete``) against the relation's test triples.
+``fold_in_evaluation`` measures entity fold-in (``Engine.fold_in``): entities
+held out of training get their rows from a share of their triples with the
+trained model frozen, and their remaining triples are ranked before and after.
 """
 from __future__ import annotations
 
@@ -279,3 +282,76 @@ def completion(eng, ds, k, *, constrained=True, exclude_loops=True, relations=No
         np.ascontiguousarray(relations, dtype=np.int32).reshape(-1)
     heads, tails, _, found = eng.complete(rels, k, known, constrained=constrained, exclude_loops=exclude_loops)
     return completion_metrics(heads, tails, found, rels, ds.test, known, k)
+
+
+def fold_in_split(ds, held_out, support=0.5):
+    """The data of a fold-in experiment.  Returns (train, support, query, known):
+    `train` = the training triples that mention no held-out entity; the distinct
+    triples of all three splits that mention exactly one held-out entity are
+    divided per held-out entity, in the order train, valid, test, into its first
+    ceil(support * m) triples (`support`, the fold-in examples; at least one) and
+    the rest (`query`); `known` = every triple of the three splits.  A triple with
+    two held-out entities can be neither an example nor a fair query and is left
+    out."""
+    held = np.unique(np.asarray(held_out, dtype=np.int64).reshape(-1))
+    known = np.concatenate([ds.train, ds.valid, ds.test]).astype(np.int32)
+    train = np.asarray(ds.train, dtype=np.int32)
+    train = train[~(np.isin(train[:, 0], held) | np.isin(train[:, 1], held))]
+    _, first = np.unique(known, axis=0, return_index=True)
+    distinct = known[np.sort(first)]
+    hh, ht = np.isin(distinct[:, 0], held), np.isin(distinct[:, 1], held)
+    one = distinct[hh ^ ht]
+    owner = np.where(np.isin(one[:, 0], held), one[:, 0], one[:, 1])
+    sup, qry = [], []
+    for e in held.tolist():
+        mine = one[owner == e]
+        k = min(len(mine), max(1, int(np.ceil(support * len(mine))))) if len(mine) else 0
+        sup.append(mine[:k])
+        qry.append(mine[k:])
+    empty = np.zeros((0, 3), np.int32)
+    return (train, np.concatenate(sup + [empty]).astype(np.int32), np.concatenate(qry + [empty]).astype(np.int32),
+            known)
+
+
+def fold_in_evaluation(ds, model, dim, held_out, *, support=0.5, epochs=50, fold_epochs=50, fold_seed=0, side=2,
+                       rate=0.001, margin=1.0, method=1, distance=0, batches=100, seed=7, schedule="ordered",
+                       device=0, make_engine=Engine):
+    """Hold entities out, train without them, fold them in, and rank what is left:
+    every triple that mentions a held-out entity is removed from training
+    (``fold_in_split``), the model is trained `epochs` epochs on the rest, the
+    held-out entities are folded in from the `support` share of their triples
+    (``Engine.fold_in``, `fold_epochs` passes, known = all triples), and their
+    remaining triples are ranked (``Engine.rank_triples``, filtered) first with
+    the rows the held-out entities had after training -- their initial rows, which
+    no training sample touched -- and then with the folded rows.  Returns
+    {"held_out", "support", "query", "rank_before", "rank_after" (filtered mean
+    rank over both sides), "hits10_before", "hits10_after", "loss_first",
+    "loss_last" (summed over the held-out entities), "active", "failed",
+    "capped", "rows"}."""
+    held = np.unique(np.asarray(held_out, dtype=np.int32).reshape(-1))
+    train, sup, qry, known = fold_in_split(ds, held, support)
+    if len(qry) == 0:
+        raise ValueError("no query triples: the held-out entities have too few triples")
+    eng = make_engine(model, dim, ds.num_entities, ds.num_relations, rate=rate, margin=margin, method=method,
+                      distance=distance, batches=batches, seed=seed, transr_compat=False, device=device,
+                      schedule=schedule)
+    try:
+        eng.upload_triples(train)
+        ent, rel, _ = eng.init_params()
+        if model in ("R", "transr", 2):
+            eng.transr_seed(ent, rel)
+        for _ in range(epochs):
+            eng.train_epoch()
+        eng.synchronize()
+        before = np.asarray(eng.rank_triples(qry, known)).reshape(-1, 4)
+        rows, loss, counts = eng.fold_in(held, sup, known, epochs=fold_epochs, seed=fold_seed, side=side)
+        after = np.asarray(eng.rank_triples(qry, known)).reshape(-1, 4)
+    finally:
+        eng.close()
+    filt = [1, 3]
+    return {"held_out": int(len(held)), "support": int(len(sup)), "query": int(len(qry)),
+            "rank_before": float(before[:, filt].mean()), "rank_after": float(after[:, filt].mean()),
+            "hits10_before": float((before[:, filt] <= 10).mean()), "hits10_after": float((after[:, filt] <= 10).mean()),
+            "loss_first": float(loss[:, 0].sum()), "loss_last": float(loss[:, 1].sum()),
+            "active": int(counts[:, 0].sum()), "failed": int(counts[:, 1].sum()), "capped": int(counts[:, 2].sum()),
+            "rows": rows}
