@@ -486,7 +486,7 @@ kb2e_status kb2e_complete_triples(kb2e_ctx* ctx, const int32_t* relations, int64
  * max_sweeps < 0, an id out of range, a free id listed twice, an example with
  * no free entity or with a free entity in both slots (the same one or two
  * different ones), a NULL array with a count > 0.  KB2E_ESTATE: no embeddings
- * on the device.  Folding in new relations is not offered. */
+ * on the device.  New relations are folded in by kb2e_fold_in_relations. */
 kb2e_status kb2e_fold_in_entities(kb2e_ctx* ctx, const int32_t* free_entities, int64_t nfree,
                                   const int32_t* heads, const int32_t* tails, const int32_t* relations, int64_t count,
                                   const int32_t* known_heads, const int32_t* known_tails,
@@ -494,6 +494,98 @@ kb2e_status kb2e_fold_in_entities(kb2e_ctx* ctx, const int32_t* free_entities, i
                                   int32_t side, int32_t max_sweeps, const double* rows_in /* [nfree][dim] or NULL */,
                                   double* rows_out /* [nfree][dim] or NULL */, double* loss /* [nfree][2] */,
                                   int64_t* counts /* [nfree][3] */);
+
+/* ---- Relation fold-in: give new relations their parameters without
+ * retraining.  For each free relation rho the call learns its row of the
+ * relation table, for TransH also its normal w and for TransR also its matrix W,
+ * from example triples, while everything else is frozen: the entity table, every
+ * other relation's rows, the training state, the glibc stream, the TransR work
+ * vectors and kb2e_device_bytes are the same, bit for bit, before and after, and
+ * training may continue afterwards.  Every model, distance, precision and dim a
+ * context takes.  The call synchronises the stream first and last.
+ *   In one sentence: for each free relation, the reference's `prebatch;
+ *   train_kb ...; postbatch` (common/trainer.cpp:69-149) over that relation's
+ *   examples, with every statement that writes an entity row removed.
+ *   Working precision: working values are FP64; FP32 tables are widened on load
+ *   and the free rows are rounded once, at the final store.
+ *   Examples and batches: every example's relation must be a free relation.  Per
+ *   free relation the call runs `epochs` passes over its examples in the caller's
+ *   order; a pass is cut into consecutive batches of batch_size samples, the last
+ *   one may be shorter, and a batch_size above the relation's example count means
+ *   one batch.  batch_size = 1 is the reference's one-sample batch, the rule
+ *   kb2e_fold_in_entities uses.  Free relations do not interact; the result
+ *   depends neither on their order nor on the launch geometry.
+ *   Per sample (pass p, example i = its index in the caller's arrays, triple
+ *   (h, t, rho)): the slot and the negative are kb2e_fold_in_entities' steps 1
+ *   and 2 -- the same stateless SplitMix64 stream with the counter p * count + i,
+ *   side 0 / 1 / 2 and 32 draws; a draw is rejected if it equals the entity it
+ *   replaces or if the new triple is among `known` or the examples.  There is no
+ *   free-entity rule: every entity row is frozen and readable.  Without an
+ *   accepted draw the sample is skipped and counted as failed.
+ *   Phase 1, at the batch's snapshot (rho's parameters as the batch finds
+ *   them): E+ and E- are kb2e_score_triples' stateless formulas (transr_compat is
+ *   ignored, the work vectors are zero).  A sample is active iff E+ + g > E-; it
+ *   then adds g + E+ - E- to the pass's loss, which is summed in sample order.
+ *   For each triple of an active sample the quantities of the reference's
+ *   gradientUpdate are taken from the snapshot only: x_k = 2 (t'_k - h'_k - r_k)
+ *   of the model's features (under L1: 1 if that is > 0, else -1); TransH also
+ *   headSum = w.h, tailSum = w.t and sum_x = sum_k x_k w_k; TransR x_k from the
+ *   projections by the snapshot W.
+ *   Phase 2, in sample order, on the working copy of rho's parameters: for every
+ *   active sample the positive triple with b = -1, then the corrupted triple with
+ *   b = +1.  Per triple (head h, tail t):
+ *     TransE (transe/trainer.cpp:28-45): r_k -= b lr x_k; norm(r), which scales
+ *       to unit length only if |r| > 1.
+ *     TransH (transh/trainer.cpp:18-58): r_k -= b lr x_k; w_k += b lr x_k
+ *       headSum; w_k -= b lr x_k tailSum; w_k += b lr sum_x h_k; w_k -= b lr sum_x
+ *       t_k; norm(r); norm(w, false); norm(r, w, lr) exactly, including its
+ *       running `sum` (common/utils.cpp:79-111); then norm(h, w, lr) and
+ *       norm(t, w, lr) with the statement that writes the entity
+ *       (a[i] -= rate * b[i]) removed, so w alone moves.
+ *     TransR (transr/trainer.cpp:147-187): W[j][i] -= b lr x_i (h_j - t_j);
+ *       r_i -= b lr x_i; norm(r, false); every row of W normed with false; then
+ *       transRNorm for the head, the tail and the reference's third call -- on
+ *       the entity whose id is the relation's id (trainer.cpp:187), skipped when
+ *       that id >= |E| -- with a[j] -= ... removed.  With a frozen the columns
+ *       decouple and a sweep is exactly W -= 2 lr a (x) (aW): no O(lr^2)
+ *       deviation remains, unlike kb2e_fold_in_entities.
+ *   Every loop against an entity row, and the r / w loop of TransH, makes at most
+ *   max_sweeps steps (0 means 10000); one that still fails its test then stops
+ *   (TransH: with the closing norm(w, false) still applied) and counts as capped.
+ *   The cap is a safety bound, not a tuning knob.
+ *   For TransE this is the reference's batch with the entity rows put back, bit
+ *   for bit up to the order of sums; for TransH and TransR the same holds
+ *   whenever no loop against an entity row fires.
+ * rel_in [nfree][dim] and w_in [nfree][dim] (TransH) / [nfree][dim][dim]
+ * (TransR, [j][i] as the weight table) give the parameters to start from (NULL:
+ * as they stand in the tables); rel_out and w_out (may be NULL) receive them as
+ * stored; loss[f*2 + 0..1] = the first and the last pass's loss of free relation
+ * f; counts[f*3 + 0..2] = its active, failed and capped counts over all passes.
+ * A free relation without examples is legal: its parameters are rel_in's / w_in's
+ * or unchanged and its loss is 0.  nknown == 0 and count == 0 with NULL arrays
+ * are legal.
+ * One 256-thread workgroup owns one free relation for all passes: phase 1
+ * spreads a batch's samples over its four waves and leaves one record a sample
+ * (in LDS while a batch's records fit 32 KiB, else in a scratch of min(batch_size,
+ * longest relation) * 2 (dim + 4) doubles per workgroup, allocated in the call and
+ * freed before it returns), phase 2 applies the records in order.  The TransR
+ * matrix lives in LDS up to dim = 131 and in a global scratch above
+ * (KB2E_FOLDREL_W_L2=1 forces that; KB2E_FOLDREL_GRID=<n> caps the workgroups:
+ * tests).
+ * KB2E_EINVAL: nfree < 1, epochs < 1, batch_size < 1, a side other than 0 / 1 /
+ * 2, max_sweeps < 0, an id out of range, a free relation listed twice, an example
+ * whose relation is not free, a NULL array with a count > 0, w_in / w_out given
+ * for TransE.  KB2E_ESTATE: no embeddings on the device. */
+kb2e_status kb2e_fold_in_relations(kb2e_ctx* ctx, const int32_t* free_relations, int64_t nfree,
+                                   const int32_t* heads, const int32_t* tails, const int32_t* relations, int64_t count,
+                                   const int32_t* known_heads, const int32_t* known_tails,
+                                   const int32_t* known_relations, int64_t nknown, int32_t epochs, int64_t batch_size,
+                                   uint64_t seed, int32_t side, int32_t max_sweeps,
+                                   const double* rel_in /* [nfree][dim] or NULL */,
+                                   const double* w_in /* [nfree][dim or dim*dim] or NULL */,
+                                   double* rel_out /* [nfree][dim] or NULL */,
+                                   double* w_out /* [nfree][dim or dim*dim] or NULL */, double* loss /* [nfree][2] */,
+                                   int64_t* counts /* [nfree][3] */);
 
 /* Raw glibc stream access (the context's RNG, as std::rand() in the reference). */
 int32_t kb2e_rng_next(kb2e_ctx* ctx);
@@ -508,7 +600,7 @@ int32_t kb2e_rng_next(kb2e_ctx* ctx);
  * "classify_sort" (every radix pass), "classify_fit" (segment starts and both
  * sweeps); kb2e_corrupt_triples: "classify_corrupt"; kb2e_complete_triples:
  * "complete_score" (projection + the tile kernel), "complete_select";
- * kb2e_fold_in_entities: "foldin").  Returns total
+ * kb2e_fold_in_entities: "foldin"; kb2e_fold_in_relations: "foldrel").  Returns total
  * milliseconds and launch count since kb2e_profile_enable.  on = 0: off;
  * on = P >= 1: the batch kernels of every P-th batch are timed (event records
  * cost device time of their own; sampling keeps the rest of the run unperturbed),
@@ -525,6 +617,8 @@ kb2e_status kb2e_profile_query(kb2e_ctx* ctx, const char* name, double* total_ms
  * "complete_candidates" -- pairs scored, "complete_records" -- records
  * appended, "complete_strips" -- score + select steps,
  * "complete_buffer_records" -- the record buffer's capacity in records.
+ * A constant of the build: "foldrel_lds_limit" -- the widest TransR matrix
+ * kb2e_fold_in_relations keeps in LDS.
  * KB2E_EINVAL for an unknown name. */
 kb2e_status kb2e_counter(kb2e_ctx* ctx, const char* name, int64_t* value);
 

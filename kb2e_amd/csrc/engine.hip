@@ -32,6 +32,7 @@
 #include "classify.hpp"
 #include "complete.hpp"
 #include "foldin.hpp"
+#include "foldrel.hpp"
 #include "host_data.hpp"
 #include "kernels_common.hpp"
 #include "kernels_index.hpp"
@@ -2083,6 +2084,31 @@ kb2e_status kb2e_fold_in_entities(kb2e_ctx* c, const int32_t* free_entities, int
     });
 }
 
+kb2e_status kb2e_fold_in_relations(kb2e_ctx* c, const int32_t* free_relations, int64_t nfree, const int32_t* heads,
+                                   const int32_t* tails, const int32_t* relations, int64_t count, const int32_t* kh,
+                                   const int32_t* kt, const int32_t* kr, int64_t nknown, int32_t epochs,
+                                   int64_t batch_size, uint64_t seed, int32_t side, int32_t max_sweeps,
+                                   const double* rel_in, const double* w_in, double* rel_out, double* w_out,
+                                   double* loss, int64_t* counts) {
+    return guarded(c, [&] {
+        if (!free_relations || nfree < 1 || !loss || !counts || count < 0 || nknown < 0 ||
+            (count > 0 && (!heads || !tails || !relations)) || (nknown > 0 && (!kh || !kt || !kr)))
+            return fail(c, KB2E_EINVAL, "no free relations, or a NULL array with a count > 0");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        fold_in_relations(eval_tables(c),
+                          FoldRelQuery{free_relations, nfree, heads, tails, relations, count, kh, kt, kr, nknown, epochs,
+                                       batch_size, seed, side, max_sweeps, c->cfg.learning_rate, c->cfg.margin, rel_in,
+                                       w_in,
+                                       // ORDERED TransR: eval_tables reads the committed matrices (wsnap); the working
+                                       // copy follows
+                                       c->cfg.model == KB2E_TRANSR && !c->parallel() ? c->w.p : nullptr},
+                          rel_out, w_out, loss, counts, &hooks);
+        return KB2E_OK;
+    });
+}
+
 int32_t kb2e_rng_next(kb2e_ctx* c) {
     if (!c) return -1;
     c->rng_version++;
@@ -2120,6 +2146,7 @@ kb2e_status kb2e_counter(kb2e_ctx* c, const char* name, int64_t* value) {
             if (nm == "complete_strips") return *value = cs.strips, KB2E_OK;
             if (nm == "complete_buffer_records") return *value = cs.buffer_records, KB2E_OK;
         }
+        if (value && nm == "foldrel_lds_limit") return *value = fold_rel_lds_limit(), KB2E_OK;  // (a constant)
         if (nm != "transh_orth_rel_batches" || !value) return fail(c, KB2E_EINVAL, "unknown counter '" + nm + "'");
         *value = 0;
         if (!c->hpar_count.p) return KB2E_OK;  // (not a PARALLEL TransH context, or no triples yet)

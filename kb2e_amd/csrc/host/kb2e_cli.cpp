@@ -8,7 +8,8 @@
 // completeTransE / completeTransH / completeTransR (knowledge-base completion:
 // the top-k new triples of each relation) and foldinTransE / foldinTransH /
 // foldinTransR (entity fold-in: rows for new entities with the trained tables
-// frozen).
+// frozen) and foldrelTransE / foldrelTransH / foldrelTransR (relation fold-in:
+// parameters for new relations with everything else frozen).
 //
 // Same flags, defaults, stdout lines and files as the reference binaries
 // (transe/bin/trainTransE.cpp, common/args.cpp, common/loader.cpp,
@@ -135,6 +136,7 @@ void printUsage(const char* invoked) {  // common/args.cpp:125-142
     printf("   --filtered [1] (completeTrans*: known = train + valid + test; 0 = train + valid)\n");
     printf("   --new FILE --foldout DIR (foldinTrans*: triples that mention the new entities; where the full entity table goes)\n");
     printf("   --epochs [1000] --seed [now] --side [2] (foldinTrans*: passes, seed of the new rows and of the negatives, slot to corrupt)\n");
+    printf("   --new FILE --foldout DIR --epochs --seed --side --batch [1] (foldrelTrans*: the new relations' triples; where the full relation tables go; samples per batch)\n");
 }
 
 EmbeddingArguments parseArgs(int argc, char** argv) {  // common/args.cpp:53-122
@@ -961,6 +963,158 @@ int foldin_main(int argc, char** argv, kb2e_model model) {
     return 0;
 }
 
+// foldrelTransE|H|R: parameters for relations the model was not trained on
+// (kb2e_fold_in_relations).  --datadir D holds relation2id.txt with the old
+// relations first and the new ones after them; relation2vec.<method> (and, for
+// TransH / TransR, weights.<method>) in --outdir O have rows for the old
+// relations only.  --new FILE lists the new relations' triples, --foldout DIR
+// receives the full relation2vec.<method> (and weights.<method>): the old
+// relations' lines byte for byte as they are in O, then the new relations' rows.
+// A new row starts as kb2e_init_params draws it for --seed; known = train +
+// valid + test + FILE.  Pass p is one call with seed --seed + p and batches of
+// --batch [1] samples; its summed loss is printed: "Pass: p, Loss: x".
+namespace {
+std::vector<std::string> read_lines(const std::string& path, const char* what) {
+    std::vector<std::string> lines;
+    FILE* f = fopen(path.c_str(), "r");
+    if (!f) {
+        printf("Could not find %s file: %s. Make sure to specify the path and/or train.\n", what, path.c_str());
+        exit(2);
+    }
+    std::string line;
+    int ch;
+    while ((ch = fgetc(f)) != EOF) {
+        line.push_back((char)ch);
+        if (ch == '\n') {
+            lines.push_back(line);
+            line.clear();
+        }
+    }
+    fclose(f);
+    return lines;
+}
+
+// n values from each of the first `rows` lines
+void parse_rows(const std::vector<std::string>& lines, size_t rows, int n, double* dst, const std::string& path) {
+    for (size_t r = 0; r < rows; ++r) {
+        const char* p = lines[r].c_str();
+        for (int k = 0; k < n; ++k) {
+            char* end = nullptr;
+            dst[r * n + k] = strtod(p, &end);
+            if (end == p) {
+                printf("Failed to read embedding values from file: '%s'\n", path.c_str());
+                exit(1);
+            }
+            p = end;
+        }
+    }
+}
+
+void write_rows(const std::string& path, const std::vector<std::string>& lines, const double* rows, size_t count, int n) {
+    FILE* out = fopen(path.c_str(), "w");
+    if (!out) {
+        printf("Could not open output file: %s\n", path.c_str());
+        exit(1);
+    }
+    for (const std::string& line : lines) fwrite(line.data(), 1, line.size(), out);
+    for (size_t f = 0; f < count; ++f) {  // common/trainer.cpp:109-127
+        for (int k = 0; k < n; ++k) fprintf(out, "%.6lf\t", rows[f * n + k]);
+        fprintf(out, "\n");
+    }
+    fclose(out);
+}
+}  // namespace
+
+int foldrel_main(int argc, char** argv, kb2e_model model) {
+    EmbeddingArguments args = parseArgs(argc, argv);
+    printf("%s\n", args.to_string().c_str());
+    int i, side = 2;
+    long long batch = 1;
+    std::string newFile, foldOut;
+    if ((i = argpos("new", true, argc, argv)) != -1) newFile = argv[i + 1];
+    if ((i = argpos("foldout", true, argc, argv)) != -1) foldOut = argv[i + 1];
+    if ((i = argpos("side", true, argc, argv)) != -1) side = atoi(argv[i + 1]);
+    if ((i = argpos("batch", true, argc, argv)) != -1) batch = atoll(argv[i + 1]);
+    if (newFile.empty() || foldOut.empty()) {
+        printf("Argument missing for %s\n", newFile.empty() ? "new" : "foldout");
+        exit(1);
+    }
+    const std::string m = method_name(args.method);
+    const std::string relPath = args.outputDir + "/relation2vec." + m, entPath = args.outputDir + "/entity2vec." + m,
+                      wPath = args.outputDir + "/weights." + m;
+    std::map<std::string, int> entity2id, relation2id;
+    loadIdFile(args.dataDir + "/entity2id.txt", entity2id);
+    loadIdFile(args.dataDir + "/relation2id.txt", relation2id);
+    const int ne = (int)entity2id.size(), nr = (int)relation2id.size(), n = args.embeddingSize;
+    // the old tables: their lines are kept as they are
+    const std::vector<std::string> rlines = read_lines(relPath, "relation embedding");
+    const int nrOld = (int)rlines.size();
+    if (nrOld < 1 || nrOld >= nr) {
+        printf("%s has %d rows and relation2id.txt %d relations: no new relation\n", relPath.c_str(), nrOld, nr);
+        exit(1);
+    }
+    const size_t wper = model == KB2E_TRANSE ? 0 : model == KB2E_TRANSH ? (size_t)n : (size_t)n * n;  // doubles a relation
+    std::vector<std::string> wlines;
+    if (wper) {
+        wlines = read_lines(wPath, "embedding weight");
+        if (wlines.size() != (size_t)nrOld * (wper / n)) {
+            printf("%s has %zu rows, not the %zu of %d relations\n", wPath.c_str(), wlines.size(),
+                   (size_t)nrOld * (wper / n), nrOld);
+            exit(1);
+        }
+    }
+    kb2e_config cfg;
+    kb2e_default_config(&cfg);
+    cfg.model = model;
+    cfg.dim = n;
+    cfg.num_entities = ne;
+    cfg.num_relations = nr;
+    cfg.learning_rate = args.learningRate;
+    cfg.margin = args.margin;
+    cfg.method = args.method;
+    cfg.distance = args.distanceType;
+    cfg.seed = args.seed;
+    cfg.precision = 64;
+    cfg.device = args.device;
+    kb2e_ctx* ctx = nullptr;
+    check(nullptr, kb2e_create(&cfg, &ctx), "create");
+    std::vector<double> E((size_t)ne * n), R((size_t)nr * n), W((size_t)nr * wper);
+    check(ctx, kb2e_init_params(ctx, E.data(), R.data(), wper ? W.data() : nullptr), "init_params");  // the new rows
+    parse_rows(rlines, (size_t)nrOld, n, R.data(), relPath);
+    if (wper) parse_rows(wlines, wlines.size(), n, W.data(), wPath);
+    check(ctx, kb2e_upload_params(ctx, E.data(), R.data(), wper ? W.data() : nullptr), "upload_params");
+    if (kb2e_read_table(ctx, 0, entPath.c_str(), KB2E_READ_VERBATIM) != KB2E_OK) {
+        printf("Failed to read embedding values from file: '%s'\n", entPath.c_str());
+        exit(1);
+    }
+
+    std::vector<int32_t> xh, xt, xr, kh, kt, kr;
+    auto addKnown = [&](int h, int t, int r) { kh.push_back(h); kt.push_back(t); kr.push_back(r); };
+    loadTripleFile(newFile, entity2id, relation2id, [&](int h, int t, int r) {
+        xh.push_back(h); xt.push_back(t); xr.push_back(r); addKnown(h, t, r); });
+    for (const char* split : {"/train.txt", "/valid.txt", "/test.txt"})
+        loadTripleFile(args.dataDir + split, entity2id, relation2id, addKnown);
+    std::vector<int32_t> free((size_t)(nr - nrOld));
+    for (int r = nrOld; r < nr; ++r) free[(size_t)(r - nrOld)] = r;
+    std::vector<double> rows(free.size() * (size_t)n), wrows(free.size() * wper), loss(free.size() * 2);
+    std::vector<int64_t> counts(free.size() * 3);
+    for (int p = 0; p < args.maxEpochs; ++p) {
+        check(ctx, kb2e_fold_in_relations(ctx, free.data(), (int64_t)free.size(), xh.data(), xt.data(), xr.data(),
+                                          (int64_t)xh.size(), kh.data(), kt.data(), kr.data(), (int64_t)kh.size(), 1,
+                                          (int64_t)batch, (uint64_t)args.seed + (uint64_t)p, side, 0, nullptr, nullptr,
+                                          rows.data(), wper ? wrows.data() : nullptr, loss.data(), counts.data()),
+              "fold_in_relations");
+        double sum = 0;
+        for (size_t f = 0; f < free.size(); ++f) sum += loss[f * 2];
+        printf("Pass: %d, Loss: %f\n", p, sum);
+        fflush(stdout);
+    }
+    write_rows(foldOut + "/relation2vec." + m, rlines, rows.data(), free.size(), n);
+    if (wper) write_rows(foldOut + "/weights." + m, wlines, wrows.data(), free.size() * (wper / n), n);
+    kb2e_destroy(ctx);
+    return 0;
+}
+
 }  // namespace kb2e_host
 
 #ifndef KB2E_CLI_NO_MAIN  // (tests/native/host_check.cpp includes this file for its parser and loader)
@@ -987,9 +1141,12 @@ int main(int argc, char** argv) {
     if (prog == "foldinTransE") return foldin_main(argc, argv, KB2E_TRANSE);
     if (prog == "foldinTransH") return foldin_main(argc, argv, KB2E_TRANSH);
     if (prog == "foldinTransR") return foldin_main(argc, argv, KB2E_TRANSR);
+    if (prog == "foldrelTransE") return foldrel_main(argc, argv, KB2E_TRANSE);
+    if (prog == "foldrelTransH") return foldrel_main(argc, argv, KB2E_TRANSH);
+    if (prog == "foldrelTransR") return foldrel_main(argc, argv, KB2E_TRANSR);
     fprintf(stderr,
-            "invoke as trainTransE|H|R, evalTransE|H|R, predictTransE|H|R, classifyTransE|H|R, completeTransE|H|R or "
-            "foldinTransE|H|R (got %s)\n",
+            "invoke as trainTransE|H|R, evalTransE|H|R, predictTransE|H|R, classifyTransE|H|R, completeTransE|H|R, "
+            "foldinTransE|H|R or foldrelTransE|H|R (got %s)\n",
             prog.c_str());
     return 2;
 }

@@ -31,6 +31,7 @@ EXPORTS = [
     "kb2e_merge_epoch_group", "kb2e_comm_info", "kb2e_get_config", "kb2e_score_triples", "kb2e_predict",
     "kb2e_rank_triples", "kb2e_predict_relations", "kb2e_rank_relations", "kb2e_fit_thresholds",
     "kb2e_classify_triples", "kb2e_corrupt_triples", "kb2e_complete_triples", "kb2e_fold_in_entities",
+    "kb2e_fold_in_relations",
 ]
 COMM_ID_BYTES = 128
 READ_VERBATIM, READ_UNIT, READ_SHRINK = 0, 1, 2
@@ -104,6 +105,8 @@ def lib():
                                             C.POINTER(i64)]),
             "kb2e_fold_in_entities": (i32, [vp, i32p, i64, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, i32, C.c_uint64,
                                             i32, i32, dp, dp, dp, C.POINTER(i64)]),
+            "kb2e_fold_in_relations": (i32, [vp, i32p, i64, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, i32, i64,
+                                             C.c_uint64, i32, i32, dp, dp, dp, dp, dp, C.POINTER(i64)]),
             "kb2e_comm_unique_id": (i32, [u8p]),
             "kb2e_comm_init_rank": (i32, [vp, i32, i32, u8p]),
             "kb2e_comm_init_group": (i32, [C.POINTER(vp), i32]),
@@ -558,6 +561,51 @@ class Engine:
                                                 _dp(rin), _dp(out), _dp(loss),
                                                 counts.ctypes.data_as(C.POINTER(C.c_int64))), "fold_in_entities")
         return out, loss, counts
+
+    # ------------------------------------------------ relation fold-in
+    def fold_in_relations(self, free, examples, known=None, *, epochs, batch_size=1, seed=0, side=2, max_sweeps=0,
+                          rel=None, w=None):
+        """Learn the parameters of the `free` relations -- their rows of the
+        relation table, for TransH also their normals, for TransR also their
+        matrices -- from the (head, tail, relation) rows of `examples`, whose
+        relations must all be free, with every entity row and every other
+        relation frozen: `epochs` passes per free relation over its examples in
+        the given order, cut into batches of `batch_size` samples (the
+        reference's batch rule: every gradient of a batch is taken at the
+        parameters the batch found, the updates are applied in sample order);
+        negatives drawn per sample (side 0 head, 1 tail, 2 a coin) from the
+        entities that do not make a row of `known` or `examples`.  `rel`
+        float64[nfree, dim] and `w` float64[nfree, dim] / [nfree, dim, dim] are
+        the parameters to start from (None: as they stand in the tables);
+        max_sweeps caps the coupling loops (0: 10000).  Returns (rel_rows
+        float64[nfree, dim] as stored, w_rows likewise or None for TransE, loss
+        float64[nfree, 2] = first and last pass, counts int64[nfree, 3] = active,
+        failed, capped); the batch is spelled out in include/kb2e_engine.h
+        (kb2e_fold_in_relations)."""
+        f = np.ascontiguousarray(free, dtype=np.int32).reshape(-1)
+        ex = np.ascontiguousarray(examples, dtype=np.int32).reshape(-1, 3)
+        ec = [np.ascontiguousarray(ex[:, k]) for k in range(3)]
+        kc, nk = self._filter_cols(known)
+        wshape = {0: None, 1: (len(f), self.n), 2: (len(f), self.n, self.n)}[self.kind]
+        rin = win = None
+        if rel is not None:
+            rin = np.ascontiguousarray(rel, dtype=np.float64)
+            if rin.shape != (len(f), self.n):
+                raise ValueError(f"rel must be [{len(f)}, {self.n}]")
+        if w is not None:
+            win = np.ascontiguousarray(w, dtype=np.float64)
+            if wshape is not None and win.shape != wshape:
+                raise ValueError(f"w must be {list(wshape)}")
+        out = np.zeros((len(f), self.n))
+        wout = None if wshape is None else np.zeros(wshape)
+        loss = np.zeros((len(f), 2))
+        counts = np.zeros((len(f), 3), np.int64)
+        self._check(lib().kb2e_fold_in_relations(self.h, _ip(f), len(f), *[_ip(c) if len(ex) else None for c in ec],
+                                                 len(ex), *[None if c is None else _ip(c) for c in kc], nk, int(epochs),
+                                                 int(batch_size), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(side),
+                                                 int(max_sweeps), _dp(rin), _dp(win), _dp(out), _dp(wout), _dp(loss),
+                                                 counts.ctypes.data_as(C.POINTER(C.c_int64))), "fold_in_relations")
+        return out, wout, loss, counts
 
     def device_bytes(self):
         return lib().kb2e_device_bytes(self.h)

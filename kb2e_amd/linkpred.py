@@ -355,3 +355,76 @@ def fold_in_evaluation(ds, model, dim, held_out, *, support=0.5, epochs=50, fold
             "loss_first": float(loss[:, 0].sum()), "loss_last": float(loss[:, 1].sum()),
             "active": int(counts[:, 0].sum()), "failed": int(counts[:, 1].sum()), "capped": int(counts[:, 2].sum()),
             "rows": rows}
+
+
+def fold_in_relations_split(ds, held_out, support=0.5):
+    """The data of a relation fold-in experiment.  Returns (train, support,
+    query, known): `train` = the training triples of the other relations; the
+    distinct triples of all three splits that belong to a held-out relation are
+    divided per held-out relation, in the order train, valid, test, into its
+    first ceil(support * m) triples (`support`, the fold-in examples; at least
+    one) and the rest (`query`); `known` = every triple of the three splits."""
+    held = np.unique(np.asarray(held_out, dtype=np.int64).reshape(-1))
+    known = np.concatenate([ds.train, ds.valid, ds.test]).astype(np.int32)
+    train = np.asarray(ds.train, dtype=np.int32)
+    train = train[~np.isin(train[:, 2], held)]
+    _, first = np.unique(known, axis=0, return_index=True)
+    distinct = known[np.sort(first)]
+    sup, qry = [], []
+    for r in held.tolist():
+        mine = distinct[distinct[:, 2] == r]
+        k = min(len(mine), max(1, int(np.ceil(support * len(mine))))) if len(mine) else 0
+        sup.append(mine[:k])
+        qry.append(mine[k:])
+    empty = np.zeros((0, 3), np.int32)
+    return (train, np.concatenate(sup + [empty]).astype(np.int32), np.concatenate(qry + [empty]).astype(np.int32),
+            known)
+
+
+def fold_in_relations_evaluation(ds, model, dim, held_out, *, support=0.5, epochs=50, fold_epochs=50, batch_size=1,
+                                 fold_seed=0, side=2, rate=0.001, margin=1.0, method=1, distance=0, batches=100,
+                                 seed=7, schedule="ordered", device=0, make_engine=Engine):
+    """Hold relations out, train without them, fold them in, and rank what is
+    left: every triple of a held-out relation is removed from training
+    (``fold_in_relations_split``; a relation without a training triple is never
+    sampled, so its parameters stay as initialised), the model is trained `epochs`
+    epochs on the rest, the held-out relations are folded in from the `support`
+    share of their triples (``Engine.fold_in_relations``, `fold_epochs` passes in
+    batches of `batch_size`, known = all triples), and their remaining triples
+    are ranked -- the entities with ``Engine.rank_triples``, the relation with
+    ``Engine.rank_relations``, both filtered -- first with the parameters the
+    held-out relations had after training and then with the folded ones.  Returns
+    fold_in_evaluation's keys ("rank_*" and "hits10_*" over both entity sides)
+    with "rel_rank_before" / "rel_rank_after" (filtered mean rank of the
+    relation) added, and "rel_rows" / "w_rows" in place of "rows"."""
+    held = np.unique(np.asarray(held_out, dtype=np.int32).reshape(-1))
+    train, sup, qry, known = fold_in_relations_split(ds, held, support)
+    if len(qry) == 0:
+        raise ValueError("no query triples: the held-out relations have too few triples")
+    eng = make_engine(model, dim, ds.num_entities, ds.num_relations, rate=rate, margin=margin, method=method,
+                      distance=distance, batches=batches, seed=seed, transr_compat=False, device=device,
+                      schedule=schedule)
+    try:
+        eng.upload_triples(train)
+        ent, rel, _ = eng.init_params()
+        if model in ("R", "transr", 2):
+            eng.transr_seed(ent, rel)
+        for _ in range(epochs):
+            eng.train_epoch()
+        eng.synchronize()
+        before = np.asarray(eng.rank_triples(qry, known)).reshape(-1, 4)
+        rel_before = np.asarray(eng.rank_relations(qry, known)).reshape(-1, 2)
+        rows, wrows, loss, counts = eng.fold_in_relations(held, sup, known, epochs=fold_epochs, batch_size=batch_size,
+                                                          seed=fold_seed, side=side)
+        after = np.asarray(eng.rank_triples(qry, known)).reshape(-1, 4)
+        rel_after = np.asarray(eng.rank_relations(qry, known)).reshape(-1, 2)
+    finally:
+        eng.close()
+    filt = [1, 3]
+    return {"held_out": int(len(held)), "support": int(len(sup)), "query": int(len(qry)),
+            "rank_before": float(before[:, filt].mean()), "rank_after": float(after[:, filt].mean()),
+            "hits10_before": float((before[:, filt] <= 10).mean()), "hits10_after": float((after[:, filt] <= 10).mean()),
+            "rel_rank_before": float(rel_before[:, 1].mean()), "rel_rank_after": float(rel_after[:, 1].mean()),
+            "loss_first": float(loss[:, 0].sum()), "loss_last": float(loss[:, 1].sum()),
+            "active": int(counts[:, 0].sum()), "failed": int(counts[:, 1].sum()), "capped": int(counts[:, 2].sum()),
+            "rel_rows": rows, "w_rows": wrows}
