@@ -92,8 +92,18 @@ class Case:
 #                    under both schedules
 #   H 260 ordered    none of 1..32 (best 4.9e-7) and TransH has no L2 distance to
 #                    fall back on; 3894 is the first of 1..8000 (1.07e-6)
+#   H 260 parallel   none of 1..8000 (3894 does not carry over: after the first batch
+#                    the two schedules' tables, and so the later sign arguments, differ)
+#   H 300            none of 1..299 under either schedule
+#   E 300 ordered L1 none of 1..199
+# So the four-chunk float builds (257 <= n <= 512) are compared under L2, where no sign
+# argument enters: seed 1 at every width under both schedules (slack 0.997: at sigma = 1 / n
+# the energies are far below the margin, every sample is active and moves its rows).  FP32
+# L1 at four chunks rests on ord-H260-L1 and, for the sign-word layout that L1 adds to L2,
+# on the FP64 cases of test_gpu_wide_rows.py, which share the float builds' templates.
 ORDERED_CASES = [
     Case("E", 17, 1), Case("E", 130, 1, distance=1), Case("E", 200, 28),
+    Case("E", 300, 1, distance=1), Case("E", 385, 1, distance=1), Case("E", 512, 1, distance=1),
     Case("H", 33, 1), Case("H", 130, 395), Case("H", 260, 3894),
     Case("R", 20, 1), Case("R", 50, 1), Case("R", 33, 2), Case("R", 64, 1),
     Case("R", 100, 1), Case("R", 190, 9), Case("R", 200, 3),
@@ -104,6 +114,8 @@ ORDERED_CASES = [
 _P = dict(schedule="parallel")
 PARALLEL_CASES = [
     Case("E", 17, 1, **_P), Case("E", 130, 35, **_P),
+    Case("E", 257, 1, distance=1, **_P), Case("E", 300, 1, distance=1, **_P),
+    Case("E", 385, 1, distance=1, **_P), Case("E", 512, 1, distance=1, **_P),
     Case("H", 33, 1, **_P), Case("H", 130, 395, **_P),
     Case("R", 20, 1, sub=1, **_P), Case("R", 50, 1, sub=1, **_P), Case("R", 100, 2, sub=1, **_P),
     Case("R", 128, 2, sub=1, **_P), Case("R", 160, 1, sub=1, **_P), Case("R", 260, 2, sub=1, **_P),

@@ -23,7 +23,7 @@ skipped relation shows at the learning-rate scale (a batch moves touched rows by
 >= 7e-2, three orders above the bar); FP32 rounding is 2^-24 a store with <= 31
 touches a row and wave sums of n <= 512 terms, a few 1e-6.
 
-All cases: precision 32, data.synthetic("tiny", seed=5), B = 100 (n = 512: 50),
+All cases: precision 32, data.synthetic("tiny", seed=5), B = 100 (ord-R512-L1: 50),
 rate 0.01, bern, TransR with the fixed (zeroed) energy.
 
 Out of scope: TransR's compat energy.  Its energies accumulate over the whole
@@ -48,6 +48,14 @@ no case needed a raised one:
                                                     par-R50-L1-subdef      9.72e-08
                                                     par-R50-L1-sub1-mfma1  6.30e-08
                                                     par-R50-L1-sub1-mfma0  7.14e-08
+
+and the four-chunk float builds of TransE (257 <= n <= 512, L2; fp32_step.py says why
+not L1):
+
+  ord-E300-L2   5.41e-09   par-E257-L2   5.56e-10
+  ord-E385-L2   4.14e-09   par-E300-L2   5.62e-10
+  ord-E512-L2   3.16e-09   par-E385-L2   4.80e-10
+                           par-E512-L2   4.24e-10
 
 The largest sit in TransR's matrices at the widest rows (n = 190 in LDS, n = 512
 from L2), a few 1e-6 as the rounding argument predicts, 2x below the bar.  (PARALLEL
@@ -93,7 +101,8 @@ def _run(case, monkeypatch):
 
 @pytest.mark.parametrize("case", fs.ORDERED_CASES, ids=lambda c: c.id)
 def test_ordered_fp32_batch_parity(case, monkeypatch):
-    """TransE n = 17 (L1), 130 (L2: two chunks, the second nearly empty), 200;
+    """TransE n = 17 (L1), 130 (L2: two chunks, the second nearly empty), 200, and L2
+    on the four-chunk build at 300 (three chunks), 385 and 512 (four, the last full);
     TransH n = 33 (one chunk, ragged), 130 (two), 260 (four, ragged last); TransR
     n = 20, 50 (named register instantiations), 33 (reg<64>), 64, 100 (LDS owner),
     190 / 200 (either side of the FP32 LDS limit of 195), 512 (B = 50), and L2 at 50."""
@@ -102,7 +111,8 @@ def test_ordered_fp32_batch_parity(case, monkeypatch):
 
 @pytest.mark.parametrize("case", fs.PARALLEL_CASES, ids=lambda c: c.id)
 def test_parallel_fp32_batch_parity(case, monkeypatch):
-    """Against oracle/parallel.py from the engine's own tables: TransE n = 17, 130;
+    """Against oracle/parallel.py from the engine's own tables: TransE n = 17, 130, and
+    L2 at 257, 300, 385, 512 (transe_score_kernel / transe_apply_kernel<float, 4, false>);
     TransH n = 33, 130; TransR n = 20, 50, 100 (generic chain), 128, 160, 260 (wide
     kernels) with sub_batches = 1, n = 50 also at the default sub-batch count and
     with KB2E_RPAR_MFMA both ways."""

@@ -12,42 +12,21 @@ import os
 import numpy as np
 import pytest
 
-from gpu_common import max_abs, tiny
+from gpu_common import P_ATOL, max_abs, parallel_vs_model, tiny
 from kb2e_amd import data
 from kb2e_amd.engine import Engine
 from oracle import orc
-from oracle.parallel import transe_parallel_batches
 
 pytestmark = pytest.mark.gpu
-
-P_ATOL = 1e-11
 
 
 def _transe_vs_model(ds, dim, epochs, *, distance=0, method=1, batches=20, rate=0.01, seed=3, apply_long=None,
                      monkeypatch=None):
     if apply_long is not None:
         monkeypatch.setenv("KB2E_APPLY_LONG", str(apply_long))
-    m = orc.Model("E", dim, ds.num_entities, ds.num_relations, rate=rate, method=method, distance=distance,
-                  batches=batches)
-    m.set_triples(ds.train)
-    orc.srand(seed)
-    m.prep_train()
-    pe, pr, _ = m.tables()
-    eng = Engine("E", dim, ds.num_entities, ds.num_relations, rate=rate, method=method, distance=distance,
-                 batches=batches, seed=seed, schedule="parallel")
-    eng.upload_triples(ds.train)
-    e0, r0, _ = eng.init_params()
-    assert np.array_equal(e0, pe) and np.array_equal(r0, pr)
-    B = m.batch_size()
-    for ep in range(epochs):
-        si, sj, side = m.sample_stream(B * batches)
-        lo, ao = transe_parallel_batches(pe, pr, ds.train, si, sj, side, B, batches, rate=rate, l1=distance == 0)
-        lg, ag = eng.train_epoch()
-        assert ag == ao, (ep, ag, ao)
-        assert abs(lg - lo) <= 1e-9 * max(1.0, abs(lo))
-        ge, gr, _ = eng.download_params()
-        assert max_abs(ge, pe) < P_ATOL and max_abs(gr, pr) < P_ATOL, (ep, max_abs(ge, pe), max_abs(gr, pr))
-    return eng
+    # (the driver itself: gpu_common.py, shared with test_gpu_wide_rows.py)
+    parallel_vs_model("E", ds, dim, epochs, distance=distance, method=method, batches=batches, rate=rate, seed=seed,
+                      atol=P_ATOL)
 
 
 @pytest.mark.parametrize("dim,distance", [(50, 0), (100, 0), (100, 1), (17, 0), (200, 0), (130, 1)])
@@ -401,29 +380,8 @@ def test_transr_parallel_fp32_close(monkeypatch):
 
 
 def _transh_vs_model(ds, dim, epochs, *, batches=10, rate=0.01, seed=3, method=1, atol=1e-9, orth_min=None):
-    from oracle.parallel import ORTH_REL_MIN, transh_parallel_batches
-    m = orc.Model("H", dim, ds.num_entities, ds.num_relations, rate=rate, method=method, batches=batches)
-    m.set_triples(ds.train)
-    orc.srand(seed)
-    m.prep_train()
-    pe, pr, pw = m.tables()
-    eng = Engine("H", dim, ds.num_entities, ds.num_relations, rate=rate, method=method, batches=batches, seed=seed,
-                 schedule="parallel")
-    eng.upload_triples(ds.train)
-    e0, r0, w0 = eng.init_params()
-    assert np.array_equal(e0, pe) and np.array_equal(r0, pr) and np.array_equal(w0, pw)
-    B = m.batch_size()
-    state = {}  # the previous batch's flagged samples, across epochs as in the engine
-    for ep in range(epochs):
-        si, sj, side = m.sample_stream(B * batches)
-        lo, ao = transh_parallel_batches(pe, pr, pw, ds.train, si, sj, side, B, batches, rate=rate, state=state,
-                                         orth_rel_min=ORTH_REL_MIN if orth_min is None else orth_min)
-        lg, ag = eng.train_epoch()
-        assert ag == ao, (ep, ag, ao)
-        assert abs(lg - lo) <= 1e-9 * max(1.0, abs(lo))
-        ge, gr, gw = eng.download_params()
-        errs = (max_abs(ge, pe), max_abs(gr, pr), max_abs(gw, pw))
-        assert max(errs) < atol, (ep, errs)
+    parallel_vs_model("H", ds, dim, epochs, method=method, batches=batches, rate=rate, seed=seed, atol=atol,
+                      orth_min=orth_min)
 
 
 @pytest.mark.parametrize("dim", [20, 100, 17, 130])

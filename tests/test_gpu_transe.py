@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from gpu_common import F32_ATOL, F64_ATOL, golden_engine, max_abs, oracle_model, tiny
+from gpu_common import F32_ATOL, F64_ATOL, golden_engine, max_abs, oracle_model, ordered_vs_oracle, tiny
 from kb2e_amd import data
 from kb2e_amd.engine import SAMPLER_GLIBC, SAMPLER_REPLAY, Engine
 from oracle import orc
@@ -58,23 +58,8 @@ def test_golden_training_run_fp32():
 
 
 def _oracle_vs_engine(ds, dim, epochs, *, distance=0, method=1, batches=20, rate=0.01, seed=3, atol=F64_ATOL):
-    m = oracle_model("E", ds, dim, rate=rate, margin=1.0, method=method, distance=distance, batches=batches)
-    orc.srand(seed)
-    m.prep_train()
-    eng = Engine("E", dim, ds.num_entities, ds.num_relations, rate=rate, margin=1.0, method=method,
-                 distance=distance, batches=batches, seed=seed)
-    eng.upload_triples(ds.train)
-    e0, r0, _ = eng.init_params()
-    oe, orl, _ = m.tables()
-    assert np.array_equal(e0, oe) and np.array_equal(r0, orl)
-    for ep in range(epochs):
-        lo, ao = m.train_epoch()
-        lg, ag = eng.train_epoch()
-        assert ag == ao, (ep, ag, ao)
-        assert abs(lg - lo) <= 1e-9 * max(1.0, abs(lo))
-        ge, gr, _ = eng.download_params()
-        oe, orl, _ = m.tables()
-        assert max_abs(ge, oe) < atol and max_abs(gr, orl) < atol, (ep, max_abs(ge, oe), max_abs(gr, orl))
+    ordered_vs_oracle("E", ds, dim, epochs, distance=distance, method=method, batches=batches, rate=rate, seed=seed,
+                      atol=atol)  # (the driver itself: gpu_common.py, shared with test_gpu_wide_rows.py)
 
 
 @pytest.mark.parametrize("dim,distance", [(50, 0), (100, 0), (100, 1), (17, 0), (200, 0), (130, 1)])

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from gpu_common import F64_ATOL, F64_ATOL_COUPLED, golden_engine, max_abs, oracle_model
+from gpu_common import F64_ATOL, F64_ATOL_COUPLED, golden_engine, max_abs, oracle_model, ordered_vs_oracle
 from kb2e_amd import data
 from kb2e_amd.engine import Engine
 from oracle import orc
@@ -71,21 +71,7 @@ def test_oracle_parity_three_chunks(dim):
     kernels): the per-update sign words must be laid out at that build's stride.
     Two epochs of the tiny set against the oracle, FP64."""
     ds = data.synthetic("tiny", seed=5)
-    kw = dict(rate=0.01, margin=1.0, method=1, batches=10)
-    m = oracle_model("H", ds, dim, **kw)
-    orc.srand(5)
-    m.prep_train()
-    eng = Engine("H", dim, ds.num_entities, ds.num_relations, seed=5, **kw)
-    eng.upload_triples(ds.train)
-    eng.init_params()
-    for ep in range(2):
-        lo, ao = m.train_epoch()
-        lg, ag = eng.train_epoch()
-        assert ag == ao, (ep, ag, ao)
-        assert abs(lg - lo) <= 1e-9 * max(1.0, abs(lo)), (ep, lg, lo)
-        err = max(max_abs(x, y) for x, y in zip(eng.download_params(), m.tables()))
-        assert err < F64_ATOL_COUPLED, (ep, err)
-    eng.close()
+    ordered_vs_oracle("H", ds, dim, 2, rate=0.01, method=1, batches=10, seed=5, atol=F64_ATOL_COUPLED)
 
 
 def test_fp32_statistically_close():
