@@ -304,6 +304,63 @@ kb2e_status kb2e_rank_relations(kb2e_ctx* ctx, const int32_t* heads, const int32
                                 int64_t ntest, const int32_t* filter_heads, const int32_t* filter_tails,
                                 const int32_t* filter_relations, int64_t nfilter, int64_t* ranks /* [ntest][2] */);
 
+/* Conjunctive queries: which entity fits several triple patterns at once
+ * ("born in X and works for Y and won Z"; or: which known entity is this
+ * record, given the triples that mention it -- the counterpart of
+ * kb2e_fold_in_entities, which embeds an entity the model does not have).  Both
+ * calls follow the contract of "Using a trained model" above.
+ *   Constraints.  Query q owns the constraints c = offsets[q] ..
+ *   offsets[q+1]-1, each (entities[c], relations[c], side[c]) in kb2e_predict's
+ *   convention: side 1, the unknown x is the tail of (entities[c], x,
+ *   relations[c]); side 0, the head of (x, entities[c], relations[c]).
+ *   offsets[0] == 0, offsets is strictly increasing and
+ *   1 <= m_q = offsets[q+1] - offsets[q] <= KB2E_JOINT_MAX_CONSTRAINTS.  A
+ *   constraint may appear twice in a query; each listing counts.
+ *   Candidates.  Every entity x is a candidate of every query, x == entities[c]
+ *   included, as in kb2e_predict.  The energy of x for constraint c is what
+ *   kb2e_score_triples returns for that triple, bit for bit.
+ *   Joint energy.  s = e_first; s += e_next; ... over the query's constraints
+ *   in the caller's order, in FP64, one rounding per addition.  The order of a
+ *   query's constraints is therefore part of the result: a permutation of them
+ *   may move the last bit of a joint energy.
+ *   Exclusion.  The filter triples form a set (duplicates count once;
+ *   nfilter == 0 with NULL arrays is legal).  A candidate is excluded iff every
+ *   one of its m_q triples is in the filter: it is then a known answer to the
+ *   whole conjunction.  A candidate that satisfies only some of the patterns
+ *   stays in.  With m_q == 1 this is kb2e_predict's rule.
+ *   kb2e_predict_joint.  Layout and ordering as kb2e_predict: per query the
+ *   found[q] = min(k, |E| - excluded) remaining candidates of smallest joint
+ *   energy in ascending (energy, entity id) order in ids[q*k + j],
+ *   energy[q*k + j]; the remaining slots hold -1 and +inf.  1 <= k <= 1024.
+ *   With m_q == 1 for every query the three outputs equal kb2e_predict's, bit
+ *   for bit.
+ *   kb2e_rank_joint.  ranks[q*2 + 0] = 1 + the candidates whose joint energy is
+ *   strictly smaller than truth[q]'s (ties are not counted above the truth);
+ *   ranks[q*2 + 1] = the same count with the excluded candidates other than
+ *   truth[q] left out.  With m_q == 1 these are the matching two columns of
+ *   kb2e_rank_triples.
+ * The queries are walked in the caller's order in chunks: a chunk is the
+ * longest run of consecutive queries whose constraint rows fit
+ * max(largest m_q of the call, the rows of |E| keys that fit 1 GiB)
+ * (KB2E_JOINT_CHUNK_ROWS=<n> lowers the 1 GiB term, for tests); a query is never
+ * split, and the chunk's joint keys -- one row per query -- are held beside its
+ * constraint rows.  Per chunk every distinct relation is projected once.
+ * KB2E_EINVAL: nq < 1, k out of range, a malformed offsets (not starting at 0,
+ * not increasing, a query with 0 or more than 64 constraints,
+ * offsets[nq] > 2^31 - 1), a side other than 0 / 1, an id out of range in a
+ * constraint, in truth or in the filter, a NULL array with a count > 0.
+ * KB2E_ESTATE: no embeddings on the device. */
+enum { KB2E_JOINT_MAX_CONSTRAINTS = 64 };
+kb2e_status kb2e_predict_joint(kb2e_ctx* ctx, const int64_t* offsets /* [nq + 1] */, const int32_t* entities,
+                               const int32_t* relations, const int32_t* side /* [offsets[nq]] */, int64_t nq, int32_t k,
+                               const int32_t* filter_heads, const int32_t* filter_tails,
+                               const int32_t* filter_relations, int64_t nfilter, int32_t* ids /* [nq][k] */,
+                               double* energy /* [nq][k] */, int32_t* found /* [nq] */);
+kb2e_status kb2e_rank_joint(kb2e_ctx* ctx, const int64_t* offsets, const int32_t* entities, const int32_t* relations,
+                            const int32_t* side, const int32_t* truth /* [nq] */, int64_t nq,
+                            const int32_t* filter_heads, const int32_t* filter_tails, const int32_t* filter_relations,
+                            int64_t nfilter, int64_t* ranks /* [nq][2] */);
+
 /* ---- Triple classification (Socher et al. 2013; TransH 4.3, TransR 4.3): a
  * triple holds iff its energy is at most the threshold of its relation, fitted
  * on labelled validation triples.  The three calls below follow the contract of
@@ -595,7 +652,9 @@ int32_t kb2e_rng_next(kb2e_ctx* ctx);
  * ("score", "fold", "apply", "relowner", "index", "sample", ...; kb2e_predict:
  * "predict_score", "predict_mask", "predict_select"; kb2e_predict_relations /
  * kb2e_rank_relations: "relpred_score" (projection + key write), "relpred_mask",
- * "relpred_select", "relpred_rank"; kb2e_fit_thresholds / kb2e_classify_triples:
+ * "relpred_select", "relpred_rank"; kb2e_predict_joint / kb2e_rank_joint:
+ * "joint_score" (projection + the constraint rows), "joint_combine" (the sums),
+ * "joint_mask", "joint_select", "joint_rank"; kb2e_fit_thresholds / kb2e_classify_triples:
  * "classify_score" (energies, and the comparison of kb2e_classify_triples),
  * "classify_sort" (every radix pass), "classify_fit" (segment starts and both
  * sweeps); kb2e_corrupt_triples: "classify_corrupt"; kb2e_complete_triples:
@@ -617,6 +676,9 @@ kb2e_status kb2e_profile_query(kb2e_ctx* ctx, const char* name, double* total_ms
  * "complete_candidates" -- pairs scored, "complete_records" -- records
  * appended, "complete_strips" -- score + select steps,
  * "complete_buffer_records" -- the record buffer's capacity in records.
+ * Of the last kb2e_predict_joint / kb2e_rank_joint call (kept on the host):
+ * "joint_chunks" -- runs of queries that shared the key buffer, "joint_rows" --
+ * constraint rows scored, "joint_projections" -- per-relation projections made.
  * A constant of the build: "foldrel_lds_limit" -- the widest TransR matrix
  * kb2e_fold_in_relations keeps in LDS.
  * KB2E_EINVAL for an unknown name. */

@@ -178,6 +178,7 @@ struct kb2e_ctx {
     uint32_t hpar_stamp = 0;
     DevBuf hpar_clk;                       // KB2E_HPAR_CLK: the w-apply workgroups' clocks (diagnostic)
     CompleteStats complete_stats;  // kb2e_complete_triples: the last call's counters (kb2e_counter)
+    JointStats joint_stats;        // kb2e_predict_joint / kb2e_rank_joint: likewise
     DevBuf hpar_count;                     // PARALLEL TransH: normOrth iterations of the last two batches, relation passes run
     uint32_t hpar_orth_min = 0;            // ... from which normOrth takes the relation pass
     int32_t hpar_orth_q = 0;               // the one-wave pass's second-sweep queue (kOrthQ)
@@ -1999,6 +2000,40 @@ kb2e_status kb2e_rank_relations(kb2e_ctx* c, const int32_t* heads, const int32_t
     });
 }
 
+kb2e_status kb2e_predict_joint(kb2e_ctx* c, const int64_t* offsets, const int32_t* entities, const int32_t* relations,
+                               const int32_t* side, int64_t nq, int32_t k, const int32_t* fh, const int32_t* ft,
+                               const int32_t* fr, int64_t nfilter, int32_t* ids, double* energy, int32_t* found) {
+    return guarded(c, [&] {
+        if (!offsets || !entities || !relations || !side || nq < 1 || !ids || !energy || !found || nfilter < 0 ||
+            (nfilter > 0 && (!fh || !ft || !fr)))
+            return fail(c, KB2E_EINVAL, "no queries");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        c->joint_stats = JointStats{};
+        predict_joint(eval_tables(c), JointQuery{offsets, entities, relations, side, nullptr, nq, k, fh, ft, fr, nfilter},
+                      ids, energy, found, &c->joint_stats, &hooks);
+        return KB2E_OK;
+    });
+}
+
+kb2e_status kb2e_rank_joint(kb2e_ctx* c, const int64_t* offsets, const int32_t* entities, const int32_t* relations,
+                            const int32_t* side, const int32_t* truth, int64_t nq, const int32_t* fh,
+                            const int32_t* ft, const int32_t* fr, int64_t nfilter, int64_t* ranks) {
+    return guarded(c, [&] {
+        if (!offsets || !entities || !relations || !side || !truth || nq < 1 || !ranks || nfilter < 0 ||
+            (nfilter > 0 && (!fh || !ft || !fr)))
+            return fail(c, KB2E_EINVAL, "no queries");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        c->joint_stats = JointStats{};
+        rank_joint(eval_tables(c), JointQuery{offsets, entities, relations, side, truth, nq, 0, fh, ft, fr, nfilter},
+                   ranks, &c->joint_stats, &hooks);
+        return KB2E_OK;
+    });
+}
+
 kb2e_status kb2e_fit_thresholds(kb2e_ctx* c, const int32_t* heads, const int32_t* tails, const int32_t* relations,
                                 const uint8_t* labels, int64_t count, double* thresholds, int64_t* counts,
                                 double* global_threshold, int64_t* global_correct) {
@@ -2145,6 +2180,12 @@ kb2e_status kb2e_counter(kb2e_ctx* c, const char* name, int64_t* value) {
             if (nm == "complete_records") return *value = cs.records, KB2E_OK;
             if (nm == "complete_strips") return *value = cs.strips, KB2E_OK;
             if (nm == "complete_buffer_records") return *value = cs.buffer_records, KB2E_OK;
+        }
+        if (value && nm.rfind("joint_", 0) == 0) {  // kb2e_predict_joint / kb2e_rank_joint: the last call
+            const JointStats& js = c->joint_stats;
+            if (nm == "joint_chunks") return *value = js.chunks, KB2E_OK;
+            if (nm == "joint_rows") return *value = js.rows, KB2E_OK;
+            if (nm == "joint_projections") return *value = js.projections, KB2E_OK;
         }
         if (value && nm == "foldrel_lds_limit") return *value = fold_rel_lds_limit(), KB2E_OK;  // (a constant)
         if (nm != "transh_orth_rel_batches" || !value) return fail(c, KB2E_EINVAL, "unknown counter '" + nm + "'");

@@ -9,7 +9,9 @@
 // the top-k new triples of each relation) and foldinTransE / foldinTransH /
 // foldinTransR (entity fold-in: rows for new entities with the trained tables
 // frozen) and foldrelTransE / foldrelTransH / foldrelTransR (relation fold-in:
-// parameters for new relations with everything else frozen).
+// parameters for new relations with everything else frozen) and jointTransE /
+// jointTransH / jointTransR (conjunctive queries: the top-k entities that fit
+// several patterns at once).
 //
 // Same flags, defaults, stdout lines and files as the reference binaries
 // (transe/bin/trainTransE.cpp, common/args.cpp, common/loader.cpp,
@@ -125,6 +127,7 @@ void printUsage(const char* invoked) {  // common/args.cpp:125-142
     printf("   --queries FILE (predictTrans*: head<TAB>tail<TAB>relation lines, ? for the unknown head, tail or relation)\n");
     printf("   --topk [10] (predictTrans*)\n");
     printf("   --filtered [1] (predictTrans*: known triples are not answers)\n");
+    printf("   --queries FILE --topk [10] --filtered [1] (jointTrans*: query<TAB>head<TAB>tail<TAB>relation lines, ? for the unknown head or tail; consecutive lines with one query token are one conjunction)\n");
     printf("   --negseed [0] (classifyTrans*: seed of the generated negatives; the test split uses seed + 1)\n");
     printf("   --constrained [1] (classifyTrans*: negatives from the entities seen in that slot of the relation)\n");
     printf("   --validlabels FILE (classifyTrans*: head<TAB>tail<TAB>relation<TAB>label lines, 1 / -1 or 0; instead of generated negatives)\n");
@@ -643,6 +646,114 @@ int predict_main(int argc, char** argv, kb2e_model model) {
     return 0;
 }
 
+// jointTransE|H|R: conjunctive queries (kb2e_predict_joint) on the tables
+// predictTrans* loads, with its flags: --queries FILE, --topk K [10], --filtered
+// 0|1 [1: an entity known (train + valid + test) for every pattern of a query is
+// no answer].  A line of FILE is "query<TAB>head<TAB>tail<TAB>relation" with a
+// literal ? for exactly one of head and tail; consecutive lines with the same
+// first token are the patterns of one query, in that order (a token that comes
+// back later starts a new query).  A line with an unknown name is reported as
+// predictTrans* reports it, and the whole query that holds it is dropped.  One
+// line per answer: query token, position (from 1), entity name, joint energy.
+int joint_main(int argc, char** argv, kb2e_model model) {
+    EmbeddingArguments args = parseArgs(argc, argv);
+    printf("%s\n", args.to_string().c_str());
+    int i, topk = 10, filtered = 1;
+    std::string queries;
+    if ((i = argpos("queries", true, argc, argv)) != -1) queries = argv[i + 1];
+    if ((i = argpos("topk", true, argc, argv)) != -1) topk = atoi(argv[i + 1]);
+    if ((i = argpos("filtered", true, argc, argv)) != -1) filtered = atoi(argv[i + 1]);
+    if (queries.empty()) {
+        printf("Argument missing for queries\n");
+        exit(1);
+    }
+    FILE* f = fopen(queries.c_str(), "r");
+    if (!f) {
+        printf("Could not open query file: %s\n", queries.c_str());
+        exit(2);
+    }
+    LoadedModel L;
+    load_model(args, model, L);
+    std::vector<std::string> names(L.entity2id.size());
+    for (const auto& kv : L.entity2id)
+        if (kv.second >= 0 && (size_t)kv.second < names.size()) names[(size_t)kv.second] = kv.first;
+    std::vector<std::string> tokens;  // of the queries kept
+    std::vector<int64_t> offsets(1, 0);
+    std::vector<int32_t> qe, qr, qs;
+    std::string cur;
+    bool open = false, bad = false;
+    auto close_query = [&] {
+        if (!open) return;
+        const size_t m = qe.size() - (size_t)offsets.back();
+        if (!bad && m > (size_t)KB2E_JOINT_MAX_CONSTRAINTS) {
+            std::cout << "Query has more than " << (int)KB2E_JOINT_MAX_CONSTRAINTS << " patterns: " << cur << std::endl;
+            bad = true;
+        }
+        if (bad || m == 0) {  // dropped whole
+            qe.resize((size_t)offsets.back());
+            qr.resize((size_t)offsets.back());
+            qs.resize((size_t)offsets.back());
+        } else {
+            offsets.push_back((int64_t)qe.size());
+            tokens.push_back(cur);
+        }
+        open = bad = false;
+    };
+    char qb[512], hb[512], tb[512], rb[512];
+    while (fscanf(f, "%511s\t%511s\t%511s\t%511s", qb, hb, tb, rb) == 4) {
+        if (!open || cur != qb) {
+            close_query();
+            cur = qb;
+            open = true;
+        }
+        const bool noHead = !strcmp(hb, "?"), noTail = !strcmp(tb, "?");
+        bool fail = false;
+        if (noHead == noTail) {
+            std::cout << "Query needs exactly one ? in the head or the tail column: " << hb << ' ' << tb << std::endl;
+            fail = true;
+        }
+        if (!noHead && !L.entity2id.count(hb)) {
+            std::cout << "Head entity found in triple file that was not found in the identity file: " << hb << std::endl;
+            fail = true;
+        }
+        if (!noTail && !L.entity2id.count(tb)) {
+            std::cout << "Tail entity found in triple file that was not found in the identity file: " << tb << std::endl;
+            fail = true;
+        }
+        if (!L.relation2id.count(rb)) {
+            std::cout << "Relation found in triple file that was not found in the identity file: " << rb << std::endl;
+            fail = true;
+        }
+        if (fail) {
+            bad = true;
+            continue;
+        }
+        qe.push_back(L.entity2id[noTail ? hb : tb]);
+        qr.push_back(L.relation2id[rb]);
+        qs.push_back(noTail ? 1 : 0);
+    }
+    close_query();
+    fclose(f);
+    const size_t nq = tokens.size(), k = (size_t)std::max(topk, 1);
+    if (nq == 0) {
+        printf("No queries to answer\n");
+        kb2e_destroy(L.ctx);
+        return 0;
+    }
+    const int64_t nf = filtered ? (int64_t)L.fh.size() : 0;
+    const int32_t *fh = nf ? L.fh.data() : nullptr, *ft = nf ? L.ft.data() : nullptr, *fr = nf ? L.fr.data() : nullptr;
+    std::vector<int32_t> ids(nq * k), found(nq);
+    std::vector<double> energy(nq * k);
+    check(L.ctx, kb2e_predict_joint(L.ctx, offsets.data(), qe.data(), qr.data(), qs.data(), (int64_t)nq, topk, fh, ft, fr,
+                                    nf, ids.data(), energy.data(), found.data()), "predict_joint");
+    for (size_t q = 0; q < nq; ++q)
+        for (int j = 0; j < found[q]; ++j)
+            printf("%s\t%d\t%s\t%.6lf\n", tokens[q].c_str(), j + 1, names[(size_t)ids[q * k + j]].c_str(),
+                   energy[q * k + j]);
+    kb2e_destroy(L.ctx);
+    return 0;
+}
+
 // classifyTransE|H|R: triple classification (Socher et al. 2013; TransH 4.3,
 // TransR 4.3) of the tables evalTrans* loads.  Per-relation thresholds are
 // fitted on the valid split and applied to the test split.  A split is either
@@ -1144,9 +1255,12 @@ int main(int argc, char** argv) {
     if (prog == "foldrelTransE") return foldrel_main(argc, argv, KB2E_TRANSE);
     if (prog == "foldrelTransH") return foldrel_main(argc, argv, KB2E_TRANSH);
     if (prog == "foldrelTransR") return foldrel_main(argc, argv, KB2E_TRANSR);
+    if (prog == "jointTransE") return joint_main(argc, argv, KB2E_TRANSE);
+    if (prog == "jointTransH") return joint_main(argc, argv, KB2E_TRANSH);
+    if (prog == "jointTransR") return joint_main(argc, argv, KB2E_TRANSR);
     fprintf(stderr,
             "invoke as trainTransE|H|R, evalTransE|H|R, predictTransE|H|R, classifyTransE|H|R, completeTransE|H|R, "
-            "foldinTransE|H|R or foldrelTransE|H|R (got %s)\n",
+            "foldinTransE|H|R, foldrelTransE|H|R or jointTransE|H|R (got %s)\n",
             prog.c_str());
     return 2;
 }

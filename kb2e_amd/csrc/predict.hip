@@ -33,6 +33,11 @@
 // keys[query][|R|] with kernels of its own -- relpred_direct_kernel for TransE /
 // TransH, relpred_project_kernel + relpred_pair_kernel for TransR -- and shares
 // the mask and the selection; relpred_rank_kernel counts the per-triple ranks.
+//
+// Conjunctive queries (kb2e_predict_joint, kb2e_rank_joint: several one-sided
+// patterns about one unknown entity) score every pattern as a row with
+// predict_score_kernel, add a query's rows with joint_combine_kernel and share
+// the mask, the selection and the rank count (the last section of this file).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,6 +51,7 @@
 
 #include "eval_shared.hpp"
 #include "hip_util.hpp"
+#include "joint_host.hpp"
 #include "kernels_common.hpp"
 #include "predict.hpp"
 #include "predict_host.hpp"
@@ -1010,6 +1016,236 @@ void rank_relations(const EvalTables& t, const RelationQuery& q, int64_t* ranks,
     if (!q.truth) throw std::invalid_argument("rank_relations needs the true relations");
     if (t.f64) run_relations<double>(t, q, nullptr, nullptr, nullptr, ranks, hooks);
     else run_relations<float>(t, q, nullptr, nullptr, nullptr, ranks, hooks);
+}
+
+// ------------------------------------------------------------ conjunctive queries
+//
+// Query q owns 1..64 constraint rows, each one of predict_topk's one-sided
+// patterns.  Every row is scored by predict_score_kernel into a row buffer
+// (relation by relation, one projection per distinct relation of the chunk);
+// joint_combine_kernel adds a query's rows in the caller's order into the
+// query's key row, and the mask, the selection and the rank count run on those
+// key rows unchanged -- the keys are sums of energies >= +0, so still >= +0.
+
+namespace {
+
+struct CombineArgs {
+    const uint64_t* rows;   // [chunk rows][ne] energies as bit patterns, in scoring (relation) order
+    const int32_t* rowidx;  // [chunk rows] caller row -> its row of `rows`
+    const int32_t* qoff;    // [chunk queries + 1] caller rows of each query
+    int32_t ne, xblocks;
+    uint64_t* keys;  // [chunk queries][ne]
+};
+
+// One thread per (query, candidate): workgroup b takes candidates
+// (b % xblocks) * 256 .. of query b / xblocks (a flat grid: the queries of a
+// chunk may outnumber grid.y).  The query's row list sits in LDS, so every row
+// base is workgroup-uniform; the lanes run along the candidates (512-byte
+// segments per wave and row).  The loads of four rows are issued together; the
+// additions stay serial in the caller's order, one rounding each.
+__global__ __launch_bounds__(256) void joint_combine_kernel(CombineArgs a) {
+    __shared__ int32_t ridx[kJointMaxConstraints];
+    const int q = blockIdx.x / a.xblocks;
+    const int c0 = a.qoff[q], m = a.qoff[q + 1] - c0;
+    if ((int)threadIdx.x < m) ridx[threadIdx.x] = a.rowidx[c0 + threadIdx.x];
+    __syncthreads();
+    const int x = (blockIdx.x % a.xblocks) * blockDim.x + threadIdx.x;
+    if (x >= a.ne) return;
+    const uint64_t* col = a.rows + x;
+    double s = __longlong_as_double((long long)col[(int64_t)ridx[0] * a.ne]);
+    int j = 1;
+    for (; j + 4 <= m; j += 4) {
+        double v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = __longlong_as_double((long long)col[(int64_t)ridx[j + u] * a.ne]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s += v[u];
+    }
+    for (; j < m; ++j) s += __longlong_as_double((long long)col[(int64_t)ridx[j] * a.ne]);
+    a.keys[(int64_t)q * a.ne + x] = (uint64_t)__double_as_longlong(s);
+}
+
+constexpr int64_t kScoreMaxRows = (int64_t)65535 * kQ;  // grid.y of one score launch
+
+// predict_joint (ids / energy / found) when q.truth is null, else rank_joint (ranks).
+void run_joint(const EvalTables& t, const JointQuery& q, int32_t* ids, double* energy, int32_t* found, int64_t* ranks,
+               JointStats* stats, const PredictHooks* hooks) {
+    const int ne = t.ne, n = t.n, k = q.k;
+    const bool ranking = q.truth != nullptr;
+    if (q.nq < 1) throw std::invalid_argument("no queries");
+    if (q.nq > INT32_MAX) throw std::invalid_argument("too many queries in one call");
+    if (!ranking && (k < 1 || k > kPredictMaxK))
+        throw std::invalid_argument("k must be in 1.." + std::to_string(kPredictMaxK));
+    if (const char* why = joint_check_offsets(q.offsets, q.nq)) throw std::invalid_argument(why);
+    const int64_t nq = q.nq, nrows = q.offsets[nq];
+    for (int64_t c = 0; c < nrows; ++c) {
+        if (q.side[c] != 0 && q.side[c] != 1) throw std::invalid_argument("constraint side must be 0 (head) or 1 (tail)");
+        if (q.ent[c] < 0 || q.ent[c] >= ne || q.rel[c] < 0 || q.rel[c] >= t.nr)
+            throw std::invalid_argument("constraint " + std::to_string(c) + " has an id out of range");
+    }
+    if (ranking)
+        for (int64_t x = 0; x < nq; ++x)
+            if (q.truth[x] < 0 || q.truth[x] >= ne)
+                throw std::invalid_argument("query " + std::to_string(x) + " has a truth out of range");
+    for (int64_t x = 0; x < q.nfilter; ++x)
+        if (q.fh[x] < 0 || q.fh[x] >= ne || q.ft[x] < 0 || q.ft[x] >= ne || q.fr[x] < 0 || q.fr[x] >= t.nr)
+            throw std::invalid_argument("filter triple out of range");
+
+    // excluded per query: the candidates known for every one of its constraints
+    const JointKnown jk = joint_intersect_known(
+        q.offsets, nq, build_known_candidates(q.ent, q.rel, q.side, nrows, q.fh, q.ft, q.fr, q.nfilter, t.nr));
+
+    // scored rows held at a time: <= 1 GiB (KB2E_JOINT_CHUNK_ROWS lowers that: tests), but
+    // never less than the largest query; the key rows, one per query, come on top
+    int64_t cap = std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)ne * 8));
+    if (const long v = env_long("KB2E_JOINT_CHUNK_ROWS"); v >= 1) cap = std::min<int64_t>(cap, v);
+    const std::vector<JointChunk> chunks = joint_plan_chunks(q.offsets, nq, cap);
+    int64_t maxr = 0, maxq = 0;
+    for (const JointChunk& ch : chunks) {
+        maxr = std::max(maxr, q.offsets[ch.q1] - q.offsets[ch.q0]);
+        maxq = std::max(maxq, ch.q1 - ch.q0);
+    }
+    // the score and selection forms: predict_topk's rules
+    const bool rows_lds = (size_t)(kQ + 1) * n * 8 <= kLdsMax && !env_on("KB2E_EVAL_ROWS_L2");
+    const size_t score_lds = rows_lds ? (size_t)(kQ + 1) * n * 8 : 0;
+    const size_t staged = kSelScratchBytes + (size_t)ne * 8;
+    const char* kl2 = getenv("KB2E_PREDICT_KEYS_L2");
+    bool keys_lds = staged <= kLdsMax / 4;
+    if (kl2 && kl2[0] == '1') keys_lds = false;
+    if (kl2 && kl2[0] == '0') keys_lds = staged <= kLdsMax;
+    const size_t select_lds = kSelScratchBytes + (keys_lds ? (size_t)ne * 8 : 0);
+    if (rows_lds) allow_lds(predict_score_kernel<true>, score_lds);
+    if (!ranking && keys_lds) allow_lds(predict_select_kernel<true>, select_lds);
+
+    std::vector<int32_t> group((size_t)nq);  // one list per query
+    std::iota(group.begin(), group.end(), 0);
+    DevBuf d_e, d_s, d_ridx, d_qoff, d_g, d_off, d_kid, d_truth, d_rows, d_keys, d_PT, d_relv, d_ids, d_en, d_found,
+        d_ranks;
+    d_g.alloc((size_t)nq * 4);
+    d_off.alloc(jk.off.size() * 8);
+    d_kid.alloc(jk.ids.size() * 4);
+    HIPCHK(hipMemcpyAsync(d_g.p, group.data(), (size_t)nq * 4, hipMemcpyHostToDevice, t.stream));
+    HIPCHK(hipMemcpyAsync(d_off.p, jk.off.data(), jk.off.size() * 8, hipMemcpyHostToDevice, t.stream));
+    if (!jk.ids.empty())
+        HIPCHK(hipMemcpyAsync(d_kid.p, jk.ids.data(), jk.ids.size() * 4, hipMemcpyHostToDevice, t.stream));
+    if (ranking) {
+        d_truth.alloc((size_t)nq * 4);
+        HIPCHK(hipMemcpyAsync(d_truth.p, q.truth, (size_t)nq * 4, hipMemcpyHostToDevice, t.stream));
+        d_ranks.alloc((size_t)maxq * 2 * 8);
+    } else {
+        d_ids.alloc((size_t)maxq * k * 4);
+        d_en.alloc((size_t)maxq * k * 8);
+        d_found.alloc((size_t)maxq * 4);
+    }
+    d_e.alloc((size_t)maxr * 4);
+    d_s.alloc((size_t)maxr * 4);
+    d_ridx.alloc((size_t)maxr * 4);
+    d_qoff.alloc((size_t)(maxq + 1) * 4);
+    d_rows.alloc((size_t)maxr * ne * 8);
+    d_keys.alloc((size_t)maxq * ne * 8);
+    d_PT.alloc((size_t)n * ne * 8);
+    d_relv.alloc((size_t)n * 8);
+
+    // (the chunk's host arrays live until its synchronise: their copies are queued)
+    std::vector<int32_t> order, se, ss, srel, ridx, qoff;
+    const int32_t xblocks = (ne + 255) / 256;
+    int cur_rel = -1;  // the relation d_PT holds (kept across chunks)
+    for (const JointChunk& ch : chunks) {
+        const int64_t r0 = q.offsets[ch.q0], m = q.offsets[ch.q1] - r0, mq = ch.q1 - ch.q0;
+        // the chunk's rows grouped by relation (stable: the caller's order within one)
+        order.resize((size_t)m);
+        std::iota(order.begin(), order.end(), 0);
+        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return q.rel[r0 + x] < q.rel[r0 + y]; });
+        se.resize((size_t)m), ss.resize((size_t)m), srel.resize((size_t)m), ridx.resize((size_t)m);
+        for (int64_t p = 0; p < m; ++p) {
+            const int64_t c = r0 + order[(size_t)p];
+            se[(size_t)p] = q.ent[c];
+            ss[(size_t)p] = q.side[c];
+            srel[(size_t)p] = q.rel[c];
+            ridx[(size_t)order[(size_t)p]] = (int32_t)p;
+        }
+        qoff.resize((size_t)mq + 1);
+        for (int64_t x = 0; x <= mq; ++x) qoff[(size_t)x] = (int32_t)(q.offsets[ch.q0 + x] - r0);
+        HIPCHK(hipMemcpyAsync(d_e.p, se.data(), (size_t)m * 4, hipMemcpyHostToDevice, t.stream));
+        HIPCHK(hipMemcpyAsync(d_s.p, ss.data(), (size_t)m * 4, hipMemcpyHostToDevice, t.stream));
+        HIPCHK(hipMemcpyAsync(d_ridx.p, ridx.data(), (size_t)m * 4, hipMemcpyHostToDevice, t.stream));
+        HIPCHK(hipMemcpyAsync(d_qoff.p, qoff.data(), (size_t)(mq + 1) * 4, hipMemcpyHostToDevice, t.stream));
+        {
+            Span sp(hooks, "joint_score");
+            for (int64_t a0 = 0; a0 < m;) {
+                const int r = srel[(size_t)a0];
+                int64_t a1 = a0;
+                while (a1 < m && srel[(size_t)a1] == r && a1 - a0 < kScoreMaxRows) ++a1;
+                if (r != cur_rel) {
+                    project_any(t, r, d_PT.as<double>(), d_relv.as<double>());
+                    cur_rel = r;
+                    if (stats) ++stats->projections;
+                }
+                ScoreArgs sa{d_PT.as<double>(), d_relv.as<double>(), n, ne, t.l1, d_e.as<int32_t>() + a0,
+                             d_s.as<int32_t>() + a0, (int32_t)(a1 - a0), d_rows.as<uint64_t>() + a0 * ne};
+                dim3 grid((unsigned)xblocks, (unsigned)((a1 - a0 + kQ - 1) / kQ));
+                if (rows_lds) predict_score_kernel<true><<<grid, 256, score_lds, t.stream>>>(sa);
+                else predict_score_kernel<false><<<grid, 256, 0, t.stream>>>(sa);
+                HIPCHK(hipGetLastError());
+                a0 = a1;
+            }
+            sp.end();
+        }
+        {
+            Span sp(hooks, "joint_combine");
+            CombineArgs ca{d_rows.as<uint64_t>(), d_ridx.as<int32_t>(), d_qoff.as<int32_t>(), ne, xblocks,
+                           d_keys.as<uint64_t>()};
+            joint_combine_kernel<<<(unsigned)(mq * xblocks), 256, 0, t.stream>>>(ca);
+            HIPCHK(hipGetLastError());
+            sp.end();
+        }
+        if (ranking) {
+            // relpred_rank_kernel's count with the row length |E|: the truth's key is read from
+            // the unmasked row, the query's excluded candidates other than the truth are left out
+            Span sp(hooks, "joint_rank");
+            RelRankArgs ra{d_keys.as<uint64_t>(), ne, d_truth.as<int32_t>() + ch.q0, d_g.as<int32_t>() + ch.q0,
+                           d_off.as<int64_t>(), d_kid.as<int32_t>(), d_ranks.as<int64_t>()};
+            relpred_rank_kernel<<<(unsigned)mq, 256, 0, t.stream>>>(ra);
+            HIPCHK(hipGetLastError());
+            sp.end();
+            HIPCHK(hipMemcpyAsync(ranks + ch.q0 * 2, d_ranks.p, (size_t)mq * 2 * 8, hipMemcpyDeviceToHost, t.stream));
+        } else {
+            if (!jk.ids.empty()) {
+                Span sp(hooks, "joint_mask");
+                MaskArgs ma{d_keys.as<uint64_t>(), ne, d_g.as<int32_t>() + ch.q0, d_off.as<int64_t>(), d_kid.as<int32_t>()};
+                predict_mask_kernel<<<(unsigned)mq, 256, 0, t.stream>>>(ma);
+                HIPCHK(hipGetLastError());
+                sp.end();
+            }
+            Span sp(hooks, "joint_select");
+            SelectArgs sa{d_keys.as<uint64_t>(), ne, k, d_ids.as<int32_t>(), d_en.as<double>(), d_found.as<int32_t>()};
+            if (keys_lds) predict_select_kernel<true><<<(unsigned)mq, kSelThreads, select_lds, t.stream>>>(sa);
+            else predict_select_kernel<false><<<(unsigned)mq, kSelThreads, select_lds, t.stream>>>(sa);
+            HIPCHK(hipGetLastError());
+            sp.end();
+            HIPCHK(hipMemcpyAsync(ids + ch.q0 * k, d_ids.p, (size_t)mq * k * 4, hipMemcpyDeviceToHost, t.stream));
+            HIPCHK(hipMemcpyAsync(energy + ch.q0 * k, d_en.p, (size_t)mq * k * 8, hipMemcpyDeviceToHost, t.stream));
+            HIPCHK(hipMemcpyAsync(found + ch.q0, d_found.p, (size_t)mq * 4, hipMemcpyDeviceToHost, t.stream));
+        }
+        HIPCHK(hipStreamSynchronize(t.stream));
+        if (stats) {
+            ++stats->chunks;
+            stats->rows += m;
+        }
+    }
+}
+
+}  // namespace
+
+void predict_joint(const EvalTables& t, const JointQuery& q, int32_t* ids, double* energy, int32_t* found,
+                   JointStats* stats, const PredictHooks* hooks) {
+    if (q.truth) throw std::invalid_argument("predict_joint takes no true entities");
+    run_joint(t, q, ids, energy, found, nullptr, stats, hooks);
+}
+
+void rank_joint(const EvalTables& t, const JointQuery& q, int64_t* ranks, JointStats* stats, const PredictHooks* hooks) {
+    if (!q.truth) throw std::invalid_argument("rank_joint needs the true entities");
+    run_joint(t, q, nullptr, nullptr, nullptr, ranks, stats, hooks);
 }
 
 }  // namespace kb2e

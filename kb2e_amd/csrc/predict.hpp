@@ -1,7 +1,8 @@
 // predict.hpp -- using a trained model on the device: the energy of given
 // triples, the top-k candidates of one-sided queries and relation prediction.
 // Its own translation unit (predict.hip) behind kb2e_score_triples /
-// kb2e_predict / kb2e_predict_relations / kb2e_rank_relations; the stateless
+// kb2e_predict / kb2e_predict_relations / kb2e_rank_relations /
+// kb2e_predict_joint / kb2e_rank_joint; the stateless
 // FP64 energies are the evaluator's (eval.hpp, eval_shared.hpp).
 #pragma once
 
@@ -82,5 +83,35 @@ void predict_relations(const EvalTables& t, const RelationQuery& q, int32_t* ids
 // candidates of pair q (1 + the candidates of strictly smaller energy; the
 // filtered rank leaves out the other relations whose triple is in the filter).
 void rank_relations(const EvalTables& t, const RelationQuery& q, int64_t* ranks, const PredictHooks* hooks = nullptr);
+
+// Conjunctive queries: query q owns the constraint rows offsets[q] ..
+// offsets[q + 1] - 1 (1..64 of them), each a one-sided pattern (ent, rel, side)
+// as PredictQuery's; the joint energy of a candidate x is the sum of its
+// energies over those rows, added in the caller's order, and x is excluded iff
+// every one of its triples is in the filter.
+struct JointQuery {
+    const int64_t* offsets;           // [nq + 1]
+    const int32_t *ent, *rel, *side;  // [offsets[nq]]
+    const int32_t* truth;             // rank_joint: the entity to rank per query (else null)
+    int64_t nq;
+    int32_t k;                        // predict_joint: 1..kPredictMaxK
+    const int32_t *fh, *ft, *fr;
+    int64_t nfilter;
+};
+
+// The last call's numbers (kb2e_counter "joint_*").
+struct JointStats {
+    int64_t chunks = 0;       // runs of queries whose rows shared the key buffer
+    int64_t rows = 0;         // constraint rows scored
+    int64_t projections = 0;  // project_any calls
+};
+
+// ids / energy [nq][k], found [nq]: as predict_topk, on the joint energies.
+void predict_joint(const EvalTables& t, const JointQuery& q, int32_t* ids, double* energy, int32_t* found,
+                   JointStats* stats = nullptr, const PredictHooks* hooks = nullptr);
+
+// ranks[q * 2 + 0..1] = raw and filtered rank of truth[q] among the |E| candidates of query q.
+void rank_joint(const EvalTables& t, const JointQuery& q, int64_t* ranks, JointStats* stats = nullptr,
+                const PredictHooks* hooks = nullptr);
 
 }  // namespace kb2e

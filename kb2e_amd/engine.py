@@ -31,7 +31,7 @@ EXPORTS = [
     "kb2e_merge_epoch_group", "kb2e_comm_info", "kb2e_get_config", "kb2e_score_triples", "kb2e_predict",
     "kb2e_rank_triples", "kb2e_predict_relations", "kb2e_rank_relations", "kb2e_fit_thresholds",
     "kb2e_classify_triples", "kb2e_corrupt_triples", "kb2e_complete_triples", "kb2e_fold_in_entities",
-    "kb2e_fold_in_relations",
+    "kb2e_fold_in_relations", "kb2e_predict_joint", "kb2e_rank_joint",
 ]
 COMM_ID_BYTES = 128
 READ_VERBATIM, READ_UNIT, READ_SHRINK = 0, 1, 2
@@ -97,6 +97,10 @@ def lib():
             "kb2e_rank_triples": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, C.POINTER(i64)]),
             "kb2e_predict_relations": (i32, [vp, i32p, i32p, i64, i32, i32p, i32p, i32p, i64, i32p, dp, i32p]),
             "kb2e_rank_relations": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, C.POINTER(i64)]),
+            "kb2e_predict_joint": (i32, [vp, C.POINTER(i64), i32p, i32p, i32p, i64, i32, i32p, i32p, i32p, i64, i32p, dp,
+                                         i32p]),
+            "kb2e_rank_joint": (i32, [vp, C.POINTER(i64), i32p, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64,
+                                      C.POINTER(i64)]),
             "kb2e_fit_thresholds": (i32, [vp, i32p, i32p, i32p, u8p, i64, dp, C.POINTER(i64), dp, C.POINTER(i64)]),
             "kb2e_classify_triples": (i32, [vp, i32p, i32p, i32p, i64, dp, u8p, dp]),
             "kb2e_corrupt_triples": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, C.c_uint64, i32, i32,
@@ -442,6 +446,56 @@ class Engine:
         self._check(lib().kb2e_rank_relations(self.h, _ip(tc[0]), _ip(tc[1]), _ip(tc[2]), len(test),
                                               *[None if c is None else _ip(c) for c in fc], nf,
                                               ranks.ctypes.data_as(C.POINTER(C.c_int64))), "rank_relations")
+        return ranks
+
+    # ------------------------------------------------ conjunctive queries
+    @staticmethod
+    def _joint_arrays(queries):
+        """offsets int64[nq + 1] and the (entity, relation, side) columns of the
+        queries' rows, concatenated in order."""
+        rows = [np.ascontiguousarray(q, dtype=np.int32).reshape(-1, 3) for q in queries]
+        offsets = np.zeros(len(rows) + 1, np.int64)
+        if rows:
+            offsets[1:] = np.cumsum([len(r) for r in rows])
+        cat = np.concatenate(rows + [np.zeros((0, 3), np.int32)])
+        cols = [np.ascontiguousarray(cat[:, c]) for c in range(3)]
+        return offsets, cols
+
+    def predict_joint(self, queries, k, filt=None):
+        """Top-k entities that fit several patterns at once.  `queries` is a
+        sequence of int arrays [m_q, 3] of (entity, relation, side) rows, predict()'s
+        patterns, 1 <= m_q <= 64; a candidate's joint energy is the sum of its
+        energies over the query's rows, added in the given order, and it is
+        excluded iff every one of its triples is a row of `filt`.  Returns (ids
+        int32[nq, k], energy float64[nq, k], found int32[nq]) as predict()."""
+        offsets, cols = self._joint_arrays(queries)
+        nq, k = len(offsets) - 1, int(k)
+        fc, nf = self._filter_cols(filt)
+        kk = max(k, 1)
+        ids = np.full((nq, kk), -1, np.int32)
+        en = np.full((nq, kk), np.inf)
+        found = np.zeros(nq, np.int32)
+        self._check(lib().kb2e_predict_joint(self.h, offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ip(cols[0]),
+                                             _ip(cols[1]), _ip(cols[2]), nq, k,
+                                             *[None if c is None else _ip(c) for c in fc], nf, _ip(ids), _dp(en),
+                                             _ip(found)), "predict_joint")
+        return ids, en, found
+
+    def rank_joint(self, queries, truth, filt):
+        """The rank of truth[q] among all entities by the joint energy of query q
+        (predict_joint's queries), in the caller's order: int64[nq, 2] = raw, and
+        with the excluded candidates other than the truth left out."""
+        offsets, cols = self._joint_arrays(queries)
+        nq = len(offsets) - 1
+        tr = np.ascontiguousarray(truth, dtype=np.int32).reshape(-1)
+        if len(tr) != nq:
+            raise ValueError("queries and truth differ in length")
+        fc, nf = self._filter_cols(filt)
+        ranks = np.zeros((nq, 2), np.int64)
+        self._check(lib().kb2e_rank_joint(self.h, offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ip(cols[0]),
+                                          _ip(cols[1]), _ip(cols[2]), _ip(tr), nq,
+                                          *[None if c is None else _ip(c) for c in fc], nf,
+                                          ranks.ctypes.data_as(C.POINTER(C.c_int64))), "rank_joint")
         return ranks
 
     # ------------------------------------------------ triple classification

@@ -29,6 +29,9 @@ device (``Engine.complete``) against the relation's test triples.
 ``fold_in_evaluation`` measures entity fold-in (``Engine.fold_in``): entities
 held out of training get their rows from a share of their triples with the
 trained model frozen, and their remaining triples are ranked before and after.
+``entity_identification`` is its counterpart for entities the model has: the
+test triples that mention an entity, with the entity taken out, are one
+conjunctive query (``Engine.rank_joint``) that should rank it first.
 """
 from __future__ import annotations
 
@@ -428,3 +431,51 @@ def fold_in_relations_evaluation(ds, model, dim, held_out, *, support=0.5, epoch
             "loss_first": float(loss[:, 0].sum()), "loss_last": float(loss[:, 1].sum()),
             "active": int(counts[:, 0].sum()), "failed": int(counts[:, 1].sum()), "capped": int(counts[:, 2].sum()),
             "rel_rows": rows, "w_rows": wrows}
+
+
+def identification_queries(test, m_max):
+    """The mentions behind ``entity_identification``.  For every entity the
+    triples of `test` that mention it, in file order (a triple with the entity in
+    both slots is skipped), each as the pattern it leaves once the entity is
+    taken out: (tail, relation, 0) where the entity is the head -- the unknown is
+    the head of (?, tail, relation) -- and (head, relation, 1) where it is the
+    tail.  Returns (entities int32[nq], patterns list of int32[m_max, 3]): the
+    entities with at least `m_max` mentions, ascending, and their first `m_max`
+    patterns."""
+    mentions = {}
+    for h, t, r in np.asarray(test, dtype=np.int64).reshape(-1, 3).tolist():
+        if h == t:
+            continue
+        mentions.setdefault(h, []).append((t, r, 0))
+        mentions.setdefault(t, []).append((h, r, 1))
+    ents = sorted(e for e, rows in mentions.items() if len(rows) >= m_max)
+    return np.array(ents, np.int32), [np.array(mentions[e][:m_max], np.int32).reshape(-1, 3) for e in ents]
+
+
+def rank_metrics(ranks):
+    """{"mean_rank", "mrr", "hits@1", "hits@10"} of a column of ranks."""
+    ranks = np.asarray(ranks, dtype=np.float64).reshape(-1)
+    return {"mean_rank": float(ranks.mean()), "mrr": float((1.0 / ranks).mean()),
+            "hits@1": float((ranks <= 1).mean()), "hits@10": float((ranks <= 10).mean())}
+
+
+def entity_identification(eng, ds, constraints=(1, 2, 3)):
+    """Which known entity is this record?  The counterpart of entity fold-in: every
+    entity that ``ds.test`` mentions at least max(constraints) times is taken out
+    of its own test triples, and for each m of `constraints` its first m mentions
+    (``identification_queries``) are one conjunctive query whose answer should be
+    the entity: ``Engine.rank_joint`` with truth = the entity and filter = train +
+    valid + test.  Returns {m: {"count", "raw": {...}, "filtered": {...}}} with
+    mean rank, MRR, Hits@1 and Hits@10 (``rank_metrics``)."""
+    constraints = tuple(int(m) for m in constraints)
+    if not constraints or min(constraints) < 1:
+        raise ValueError("constraints must be positive")
+    ents, patterns = identification_queries(ds.test, max(constraints))
+    if len(ents) == 0:
+        raise ValueError("no entity has that many test mentions")
+    filt = np.concatenate([ds.train, ds.valid, ds.test]).astype(np.int32)
+    out = {}
+    for m in constraints:
+        ranks = np.asarray(eng.rank_joint([p[:m] for p in patterns], ents, filt)).reshape(-1, 2)
+        out[m] = {"count": int(len(ents)), "raw": rank_metrics(ranks[:, 0]), "filtered": rank_metrics(ranks[:, 1])}
+    return out
