@@ -6,12 +6,13 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -ffp-contract=off -Wall -Iinclude
 
-CSRC := $(filter-out kb2e_amd/csrc/eval.hip kb2e_amd/csrc/predict.hip kb2e_amd/csrc/eval_shared.hpp kb2e_amd/csrc/predict_host.hpp kb2e_amd/csrc/joint_host.hpp kb2e_amd/csrc/classify.hip kb2e_amd/csrc/classify_host.hpp kb2e_amd/csrc/complete.hip kb2e_amd/csrc/complete_host.hpp kb2e_amd/csrc/foldin.hip kb2e_amd/csrc/foldin_host.hpp kb2e_amd/csrc/foldrel.hip kb2e_amd/csrc/foldrel_host.hpp kb2e_amd/csrc/textio.hip kb2e_amd/csrc/transr_cons.hip kb2e_amd/csrc/kernels_transr_cons.hpp kb2e_amd/csrc/kernels_transr_wave.hpp kb2e_amd/csrc/kernels_transr_seq.hpp kb2e_amd/csrc/kernels_transr_pipe.hpp kb2e_amd/csrc/kernels_transr_chainw.hpp kb2e_amd/csrc/kernels_transr_chainwp.hpp kb2e_amd/csrc/kernels_transr_chaing.hpp kb2e_amd/csrc/transr_wide.hip kb2e_amd/csrc/kernels_transr_widep.hpp,$(wildcard kb2e_amd/csrc/*.hip kb2e_amd/csrc/*.hpp kb2e_amd/csrc/*.inc)) include/kb2e_engine.h
+CSRC := $(filter-out kb2e_amd/csrc/eval.hip kb2e_amd/csrc/predict.hip kb2e_amd/csrc/eval_shared.hpp kb2e_amd/csrc/predict_host.hpp kb2e_amd/csrc/joint_host.hpp kb2e_amd/csrc/path_host.hpp kb2e_amd/csrc/classify.hip kb2e_amd/csrc/classify_host.hpp kb2e_amd/csrc/complete.hip kb2e_amd/csrc/complete_host.hpp kb2e_amd/csrc/foldin.hip kb2e_amd/csrc/foldin_host.hpp kb2e_amd/csrc/foldrel.hip kb2e_amd/csrc/foldrel_host.hpp kb2e_amd/csrc/textio.hip kb2e_amd/csrc/transr_cons.hip kb2e_amd/csrc/kernels_transr_cons.hpp kb2e_amd/csrc/kernels_transr_wave.hpp kb2e_amd/csrc/kernels_transr_seq.hpp kb2e_amd/csrc/kernels_transr_pipe.hpp kb2e_amd/csrc/kernels_transr_chainw.hpp kb2e_amd/csrc/kernels_transr_chainwp.hpp kb2e_amd/csrc/kernels_transr_chaing.hpp kb2e_amd/csrc/transr_wide.hip kb2e_amd/csrc/kernels_transr_widep.hpp,$(wildcard kb2e_amd/csrc/*.hip kb2e_amd/csrc/*.hpp kb2e_amd/csrc/*.inc)) include/kb2e_engine.h
 
 BINS := bin/trainTransE bin/trainTransH bin/trainTransR bin/evalTransE bin/evalTransH bin/evalTransR \
 	bin/predictTransE bin/predictTransH bin/predictTransR bin/classifyTransE bin/classifyTransH bin/classifyTransR \
 	bin/completeTransE bin/completeTransH bin/completeTransR bin/foldinTransE bin/foldinTransH bin/foldinTransR \
-	bin/foldrelTransE bin/foldrelTransH bin/foldrelTransR bin/jointTransE bin/jointTransH bin/jointTransR
+	bin/foldrelTransE bin/foldrelTransH bin/foldrelTransR bin/jointTransE bin/jointTransH bin/jointTransR \
+	bin/pathTransE bin/pathTransH bin/pathTransR
 
 all: kb2e_amd/libkb2e.so bin/kb2e $(BINS) oracle bin/textio_check
 
@@ -39,8 +40,8 @@ kb2e_amd/build/eval.o: kb2e_amd/csrc/eval.hip kb2e_amd/csrc/eval.hpp kb2e_amd/cs
 	@mkdir -p kb2e_amd/build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ kb2e_amd/csrc/eval.hip
 
-# top-k queries, conjunctive queries and triple scoring (kb2e_predict, kb2e_predict_joint, kb2e_score_triples)
-kb2e_amd/build/predict.o: kb2e_amd/csrc/predict.hip kb2e_amd/csrc/predict.hpp kb2e_amd/csrc/predict_host.hpp kb2e_amd/csrc/joint_host.hpp \
+# top-k queries, conjunctive and path queries and triple scoring (kb2e_predict, kb2e_predict_joint, kb2e_predict_path, kb2e_score_triples)
+kb2e_amd/build/predict.o: kb2e_amd/csrc/predict.hip kb2e_amd/csrc/predict.hpp kb2e_amd/csrc/predict_host.hpp kb2e_amd/csrc/joint_host.hpp kb2e_amd/csrc/path_host.hpp \
 		kb2e_amd/csrc/eval.hpp kb2e_amd/csrc/eval_shared.hpp kb2e_amd/csrc/hip_util.hpp kb2e_amd/csrc/kernels_common.hpp
 	@mkdir -p kb2e_amd/build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ kb2e_amd/csrc/predict.hip
@@ -170,7 +171,7 @@ bin/san/kb2e: kb2e_amd/csrc/host/kb2e_cli.cpp kb2e_amd/csrc/classify_host.hpp in
 	$(CLANGXX) -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all -shared-libasan \
 	    -std=c++17 -Iinclude -o $@ kb2e_amd/csrc/host/kb2e_cli.cpp -Lkb2e_amd -l:libkb2e_san.so \
 	    -Wl,-rpath,'$$ORIGIN/../../kb2e_amd' -Wl,-rpath,$$(dirname $$($(CLANGXX) -print-file-name=libclang_rt.asan-x86_64.so))
-	for b in trainTransE trainTransH trainTransR evalTransE evalTransH evalTransR predictTransE predictTransH predictTransR classifyTransE classifyTransH classifyTransR completeTransE completeTransH completeTransR foldinTransE foldinTransH foldinTransR foldrelTransE foldrelTransH foldrelTransR jointTransE jointTransH jointTransR; do ln -sf kb2e bin/san/$$b; done
+	for b in trainTransE trainTransH trainTransR evalTransE evalTransH evalTransR predictTransE predictTransH predictTransR classifyTransE classifyTransH classifyTransR completeTransE completeTransH completeTransR foldinTransE foldinTransH foldinTransR foldrelTransE foldrelTransH foldrelTransR jointTransE jointTransH jointTransR pathTransE pathTransH pathTransR; do ln -sf kb2e bin/san/$$b; done
 
 clean:
 	rm -f kb2e_amd/libkb2e.so kb2e_amd/build/*.o bin/kb2e $(BINS) $(BINDING)

@@ -361,6 +361,81 @@ kb2e_status kb2e_rank_joint(kb2e_ctx* ctx, const int64_t* offsets, const int32_t
                             const int32_t* filter_heads, const int32_t* filter_tails, const int32_t* filter_relations,
                             int64_t nfilter, int64_t* ranks /* [nq][2] */);
 
+/* Path queries: the entities at the end of a relation path ("where was the
+ * spouse of X born?" is X --spouse--> ? --born_in--> ?; the intermediate entity
+ * is unknown too).  For translation models a path of relations is a sum of
+ * translations; the two calls find the cheapest instantiation of the whole path
+ * on the card.  Both follow the contract of "Using a trained model" above.
+ *   Path.  Query q starts at x_0 = anchors[q] and owns the hops c = offsets[q]
+ *   .. offsets[q+1]-1; offsets[0] == 0, offsets is strictly increasing and
+ *   1 <= L_q = offsets[q+1] - offsets[q] <= KB2E_PATH_MAX_HOPS.  Hop i
+ *   (1 .. L_q) is (relations[c], side[c]), c = offsets[q] + i - 1, in
+ *   kb2e_predict's convention: side 1, the step's triple is (x_{i-1}, x_i, r);
+ *   side 0, it is (x_i, x_{i-1}, r) -- the relation walked backwards.  Every
+ *   entity is a candidate for every x_i, the entity the hop leaves and the
+ *   anchor included; with no_loops == 1 a step with x_i == x_{i-1} is no step.
+ *   Hop energy.  What kb2e_score_triples returns for the step's triple, bit for
+ *   bit.
+ *   Path energy.  s = e_1; s += e_2; ... in hop order, FP64, one rounding per
+ *   addition.  The energy of an answer y is the minimum of s over the admissible
+ *   paths that end in y.  Rounding is monotone, so this is the recurrence
+ *   c_1[x] = e_1(x_0, x), c_i[y] = min over p of (c_{i-1}[p] + e_i(p, y)), which
+ *   is what the device computes.
+ *   Frontier.  After hop i < L_q only the frontier F_i is walked on.  beam == 0:
+ *   F_i is every entity that has a path, and the result is the exact minimum
+ *   over all |E|^(L_q - 1) intermediate tuples.  1 <= beam <= 1024: F_i is the
+ *   min(beam, entities with a path) entities of smallest (c_i, entity id) --
+ *   beam search; a beam of |E| or more gives the exact result.  The filter never
+ *   touches an intermediate hop: known facts are what a path should walk on.
+ *   Predecessor.  The predecessor of y at hop i is the p in F_{i-1} that gives
+ *   the minimum, the smallest entity id among equal sums.
+ *   Exclusion.  The filter triples form a set (duplicates count once;
+ *   nfilter == 0 with NULL arrays is legal).  Per query they are walked along
+ *   the path: S_0 = {anchor}; S_i = the entities one filter triple of hop i's
+ *   relation and side away from a member of S_{i-1} (with no_loops == 1 no
+ *   triple with h == t is taken).  y is excluded iff it is in S_{L_q}: an answer
+ *   the graph already states.  With L_q == 1 this is kb2e_predict's rule.
+ *   kb2e_predict_path.  Layout and ordering as kb2e_predict: per query the
+ *   found[q] = min(k, candidates with a path - excluded) candidates of smallest
+ *   path energy in ascending (energy, entity id) order in ids[q*k + j],
+ *   energy[q*k + j]; the remaining slots hold -1 and +inf.  1 <= k <= 1024.
+ *   via (may be NULL): via[(q*k + j)*(KB2E_PATH_MAX_HOPS-1) + i] = x_{i+1} of
+ *   the winning path of answer j for i < L_q - 1, every other slot -1.  With
+ *   L_q == 1 for every query ids, energy and found equal kb2e_predict's, bit for
+ *   bit.
+ *   kb2e_rank_path.  ranks[q*2 + 0] = 1 + the candidates whose path energy is
+ *   strictly smaller than truth[q]'s (ties are not counted above the truth; a
+ *   candidate without a path is larger than every energy); ranks[q*2 + 1] = the
+ *   same count with the excluded candidates other than truth[q] left out.  With
+ *   L_q == 1 these are the matching two columns of kb2e_rank_triples.
+ * Only the k answers, and for via the frontiers' ids and back-pointers (beam
+ * entries per level), leave the card; no key or predecessor row does.  The
+ * queries are walked in the caller's order in chunks: a chunk is the longest run
+ * of consecutive queries whose |E|-long device rows fit 1 GiB, counted in rows
+ * of |E| 4-byte words -- a query of one hop holds 2 (its key row); a longer one
+ * 3 under beam search (key row + predecessor row) and 4 + (L_q - 1) with
+ * beam == 0 (two key rows, a back-pointer row per hop 2..L_q) --
+ * (KB2E_PATH_CHUNK_ROWS=<n> lowers the budget to n such rows, for tests; it is
+ * never less than the largest query), and whose short per-query buffers
+ * (frontiers, back-pointers, answers) fit 256 MiB; a query is never split.  Per chunk and
+ * hop level every distinct relation is projected once.
+ * KB2E_EINVAL: nq < 1, k out of range, beam outside 0..1024, no_loops other than
+ * 0 / 1, a malformed offsets (not starting at 0, not increasing, a query with 0
+ * or more than 8 hops, offsets[nq] > 2^31 - 1), a side other than 0 / 1, an id
+ * out of range in an anchor, a hop, truth or the filter, a NULL array with a
+ * count > 0.  KB2E_ESTATE: no embeddings on the device. */
+enum { KB2E_PATH_MAX_HOPS = 8 };
+kb2e_status kb2e_predict_path(kb2e_ctx* ctx, const int32_t* anchors /* [nq] */, const int64_t* offsets /* [nq + 1] */,
+                              const int32_t* relations, const int32_t* side /* [offsets[nq]] */, int64_t nq, int32_t k,
+                              int32_t beam, int32_t no_loops, const int32_t* filter_heads,
+                              const int32_t* filter_tails, const int32_t* filter_relations, int64_t nfilter,
+                              int32_t* ids /* [nq][k] */, double* energy /* [nq][k] */, int32_t* found /* [nq] */,
+                              int32_t* via /* [nq][k][KB2E_PATH_MAX_HOPS - 1] or NULL */);
+kb2e_status kb2e_rank_path(kb2e_ctx* ctx, const int32_t* anchors, const int64_t* offsets, const int32_t* relations,
+                           const int32_t* side, const int32_t* truth /* [nq] */, int64_t nq, int32_t beam,
+                           int32_t no_loops, const int32_t* filter_heads, const int32_t* filter_tails,
+                           const int32_t* filter_relations, int64_t nfilter, int64_t* ranks /* [nq][2] */);
+
 /* ---- Triple classification (Socher et al. 2013; TransH 4.3, TransR 4.3): a
  * triple holds iff its energy is at most the threshold of its relation, fitted
  * on labelled validation triples.  The three calls below follow the contract of
@@ -654,7 +729,10 @@ int32_t kb2e_rng_next(kb2e_ctx* ctx);
  * kb2e_rank_relations: "relpred_score" (projection + key write), "relpred_mask",
  * "relpred_select", "relpred_rank"; kb2e_predict_joint / kb2e_rank_joint:
  * "joint_score" (projection + the constraint rows), "joint_combine" (the sums),
- * "joint_mask", "joint_select", "joint_rank"; kb2e_fit_thresholds / kb2e_classify_triples:
+ * "joint_mask", "joint_select", "joint_rank"; kb2e_predict_path / kb2e_rank_path:
+ * "path_score" (projections + hop 1), "path_hop" (the fused min-plus hops),
+ * "path_select" (frontiers, answers and their predecessors), "path_mask",
+ * "path_rank"; kb2e_fit_thresholds / kb2e_classify_triples:
  * "classify_score" (energies, and the comparison of kb2e_classify_triples),
  * "classify_sort" (every radix pass), "classify_fit" (segment starts and both
  * sweeps); kb2e_corrupt_triples: "classify_corrupt"; kb2e_complete_triples:
@@ -679,6 +757,10 @@ kb2e_status kb2e_profile_query(kb2e_ctx* ctx, const char* name, double* total_ms
  * Of the last kb2e_predict_joint / kb2e_rank_joint call (kept on the host):
  * "joint_chunks" -- runs of queries that shared the key buffer, "joint_rows" --
  * constraint rows scored, "joint_projections" -- per-relation projections made.
+ * Of the last kb2e_predict_path / kb2e_rank_path call: "path_chunks" -- runs of
+ * queries that shared the device rows, "path_hops" -- query-levels the hop
+ * kernel ran (hops 2..L of every query), "path_projections" -- per-relation
+ * projections made.
  * A constant of the build: "foldrel_lds_limit" -- the widest TransR matrix
  * kb2e_fold_in_relations keeps in LDS.
  * KB2E_EINVAL for an unknown name. */

@@ -179,6 +179,7 @@ struct kb2e_ctx {
     DevBuf hpar_clk;                       // KB2E_HPAR_CLK: the w-apply workgroups' clocks (diagnostic)
     CompleteStats complete_stats;  // kb2e_complete_triples: the last call's counters (kb2e_counter)
     JointStats joint_stats;        // kb2e_predict_joint / kb2e_rank_joint: likewise
+    PathStats path_stats;          // kb2e_predict_path / kb2e_rank_path: likewise
     DevBuf hpar_count;                     // PARALLEL TransH: normOrth iterations of the last two batches, relation passes run
     uint32_t hpar_orth_min = 0;            // ... from which normOrth takes the relation pass
     int32_t hpar_orth_q = 0;               // the one-wave pass's second-sweep queue (kOrthQ)
@@ -2034,6 +2035,43 @@ kb2e_status kb2e_rank_joint(kb2e_ctx* c, const int64_t* offsets, const int32_t* 
     });
 }
 
+kb2e_status kb2e_predict_path(kb2e_ctx* c, const int32_t* anchors, const int64_t* offsets, const int32_t* relations,
+                              const int32_t* side, int64_t nq, int32_t k, int32_t beam, int32_t no_loops,
+                              const int32_t* fh, const int32_t* ft, const int32_t* fr, int64_t nfilter, int32_t* ids,
+                              double* energy, int32_t* found, int32_t* via) {
+    return guarded(c, [&] {
+        if (!anchors || !offsets || !relations || !side || nq < 1 || !ids || !energy || !found || nfilter < 0 ||
+            (nfilter > 0 && (!fh || !ft || !fr)))
+            return fail(c, KB2E_EINVAL, "no queries");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        c->path_stats = PathStats{};
+        predict_path(eval_tables(c),
+                     PathQuery{anchors, offsets, relations, side, nullptr, nq, k, beam, no_loops, fh, ft, fr, nfilter}, ids,
+                     energy, found, via, &c->path_stats, &hooks);
+        return KB2E_OK;
+    });
+}
+
+kb2e_status kb2e_rank_path(kb2e_ctx* c, const int32_t* anchors, const int64_t* offsets, const int32_t* relations,
+                           const int32_t* side, const int32_t* truth, int64_t nq, int32_t beam, int32_t no_loops,
+                           const int32_t* fh, const int32_t* ft, const int32_t* fr, int64_t nfilter, int64_t* ranks) {
+    return guarded(c, [&] {
+        if (!anchors || !offsets || !relations || !side || !truth || nq < 1 || !ranks || nfilter < 0 ||
+            (nfilter > 0 && (!fh || !ft || !fr)))
+            return fail(c, KB2E_EINVAL, "no queries");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        c->path_stats = PathStats{};
+        rank_path(eval_tables(c),
+                  PathQuery{anchors, offsets, relations, side, truth, nq, 0, beam, no_loops, fh, ft, fr, nfilter}, ranks,
+                  &c->path_stats, &hooks);
+        return KB2E_OK;
+    });
+}
+
 kb2e_status kb2e_fit_thresholds(kb2e_ctx* c, const int32_t* heads, const int32_t* tails, const int32_t* relations,
                                 const uint8_t* labels, int64_t count, double* thresholds, int64_t* counts,
                                 double* global_threshold, int64_t* global_correct) {
@@ -2186,6 +2224,12 @@ kb2e_status kb2e_counter(kb2e_ctx* c, const char* name, int64_t* value) {
             if (nm == "joint_chunks") return *value = js.chunks, KB2E_OK;
             if (nm == "joint_rows") return *value = js.rows, KB2E_OK;
             if (nm == "joint_projections") return *value = js.projections, KB2E_OK;
+        }
+        if (value && nm.rfind("path_", 0) == 0) {  // kb2e_predict_path / kb2e_rank_path: the last call
+            const PathStats& ps = c->path_stats;
+            if (nm == "path_chunks") return *value = ps.chunks, KB2E_OK;
+            if (nm == "path_hops") return *value = ps.hops, KB2E_OK;
+            if (nm == "path_projections") return *value = ps.projections, KB2E_OK;
         }
         if (value && nm == "foldrel_lds_limit") return *value = fold_rel_lds_limit(), KB2E_OK;  // (a constant)
         if (nm != "transh_orth_rel_batches" || !value) return fail(c, KB2E_EINVAL, "unknown counter '" + nm + "'");

@@ -11,7 +11,8 @@
 // frozen) and foldrelTransE / foldrelTransH / foldrelTransR (relation fold-in:
 // parameters for new relations with everything else frozen) and jointTransE /
 // jointTransH / jointTransR (conjunctive queries: the top-k entities that fit
-// several patterns at once).
+// several patterns at once) and pathTransE / pathTransH / pathTransR (path
+// queries: the top-k entities at the end of a relation path).
 //
 // Same flags, defaults, stdout lines and files as the reference binaries
 // (transe/bin/trainTransE.cpp, common/args.cpp, common/loader.cpp,
@@ -32,9 +33,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
+#include <fstream>
 #include <functional>
 #include <iostream>
 #include <map>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -128,6 +131,7 @@ void printUsage(const char* invoked) {  // common/args.cpp:125-142
     printf("   --topk [10] (predictTrans*)\n");
     printf("   --filtered [1] (predictTrans*: known triples are not answers)\n");
     printf("   --queries FILE --topk [10] --filtered [1] (jointTrans*: query<TAB>head<TAB>tail<TAB>relation lines, ? for the unknown head or tail; consecutive lines with one query token are one conjunction)\n");
+    printf("   --queries FILE --topk [10] --beam [64] --noloops --filtered [1] (pathTrans*: anchor<TAB>relation[<TAB>relation...] lines, a relation with a leading ^ is walked backwards; --beam 0: exact)\n");
     printf("   --negseed [0] (classifyTrans*: seed of the generated negatives; the test split uses seed + 1)\n");
     printf("   --constrained [1] (classifyTrans*: negatives from the entities seen in that slot of the relation)\n");
     printf("   --validlabels FILE (classifyTrans*: head<TAB>tail<TAB>relation<TAB>label lines, 1 / -1 or 0; instead of generated negatives)\n");
@@ -754,6 +758,104 @@ int joint_main(int argc, char** argv, kb2e_model model) {
     return 0;
 }
 
+// pathTransE|H|R: path queries (kb2e_predict_path) on the tables predictTrans*
+// loads: --queries FILE, --topk K [10], --beam B [64; 0: every entity, the exact
+// minimum], --noloops [a hop may not stay on its entity], --filtered 0|1 [1: an
+// answer that train + valid + test triples themselves reach along the path is
+// no answer].  A line of FILE is "anchor<TAB>relation[<TAB>relation...]", 1..8
+// relations; a relation token with a leading ^ is walked backwards (from its
+// tail to its head).  A line with an unknown name or too many hops is reported
+// and dropped.  One line per answer: the query's line number in FILE (from 1),
+// position (from 1), entity name, path energy, and the intermediate entities of
+// the winning path joined by commas (empty for one hop).
+int path_main(int argc, char** argv, kb2e_model model) {
+    EmbeddingArguments args = parseArgs(argc, argv);
+    printf("%s\n", args.to_string().c_str());
+    int i, topk = 10, filtered = 1, beam = 64;
+    const int noloops = argpos("noloops", false, argc, argv) != -1 ? 1 : 0;
+    std::string queries;
+    if ((i = argpos("queries", true, argc, argv)) != -1) queries = argv[i + 1];
+    if ((i = argpos("topk", true, argc, argv)) != -1) topk = atoi(argv[i + 1]);
+    if ((i = argpos("beam", true, argc, argv)) != -1) beam = atoi(argv[i + 1]);
+    if ((i = argpos("filtered", true, argc, argv)) != -1) filtered = atoi(argv[i + 1]);
+    if (queries.empty()) {
+        printf("Argument missing for queries\n");
+        exit(1);
+    }
+    std::ifstream f(queries);
+    if (!f) {
+        printf("Could not open query file: %s\n", queries.c_str());
+        exit(2);
+    }
+    LoadedModel L;
+    load_model(args, model, L);
+    std::vector<std::string> names(L.entity2id.size());
+    for (const auto& kv : L.entity2id)
+        if (kv.second >= 0 && (size_t)kv.second < names.size()) names[(size_t)kv.second] = kv.first;
+    std::vector<int> lineno;  // of the queries kept
+    std::vector<int32_t> anchors, qr, qs;
+    std::vector<int64_t> offsets(1, 0);
+    std::string line;
+    for (int ln = 1; std::getline(f, line); ++ln) {
+        std::vector<std::string> tok;
+        std::istringstream is(line);
+        for (std::string w; is >> w;) tok.push_back(w);
+        if (tok.empty()) continue;
+        bool fail = false;
+        if (!L.entity2id.count(tok[0])) {
+            std::cout << "Head entity found in triple file that was not found in the identity file: " << tok[0] << std::endl;
+            fail = true;
+        }
+        if (tok.size() < 2 || tok.size() - 1 > (size_t)KB2E_PATH_MAX_HOPS) {
+            std::cout << "Query needs 1 to " << (int)KB2E_PATH_MAX_HOPS << " relations: " << tok[0] << std::endl;
+            fail = true;
+        }
+        for (size_t x = 1; x < tok.size() && !fail; ++x) {
+            const bool back = tok[x][0] == '^';
+            const std::string rn = back ? tok[x].substr(1) : tok[x];
+            if (!L.relation2id.count(rn)) {
+                std::cout << "Relation found in triple file that was not found in the identity file: " << rn << std::endl;
+                fail = true;
+                break;
+            }
+            qr.push_back(L.relation2id[rn]);
+            qs.push_back(back ? 0 : 1);
+        }
+        if (fail) {  // dropped whole
+            qr.resize((size_t)offsets.back());
+            qs.resize((size_t)offsets.back());
+            continue;
+        }
+        anchors.push_back(L.entity2id[tok[0]]);
+        offsets.push_back((int64_t)qr.size());
+        lineno.push_back(ln);
+    }
+    const size_t nq = anchors.size(), k = (size_t)std::max(topk, 1);
+    if (nq == 0) {
+        printf("No queries to answer\n");
+        kb2e_destroy(L.ctx);
+        return 0;
+    }
+    const int64_t nf = filtered ? (int64_t)L.fh.size() : 0;
+    const int32_t *fh = nf ? L.fh.data() : nullptr, *ft = nf ? L.ft.data() : nullptr, *fr = nf ? L.fr.data() : nullptr;
+    const size_t W = (size_t)KB2E_PATH_MAX_HOPS - 1;
+    std::vector<int32_t> ids(nq * k), found(nq), via(nq * k * W);
+    std::vector<double> energy(nq * k);
+    check(L.ctx, kb2e_predict_path(L.ctx, anchors.data(), offsets.data(), qr.data(), qs.data(), (int64_t)nq, topk, beam,
+                                   noloops, fh, ft, fr, nf, ids.data(), energy.data(), found.data(), via.data()),
+          "predict_path");
+    for (size_t q = 0; q < nq; ++q)
+        for (int j = 0; j < found[q]; ++j) {
+            std::string w;
+            for (size_t x = 0; x < W && via[(q * k + (size_t)j) * W + x] >= 0; ++x)
+                w += (x ? "," : "") + names[(size_t)via[(q * k + (size_t)j) * W + x]];
+            printf("%d\t%d\t%s\t%.6lf\t%s\n", lineno[q], j + 1, names[(size_t)ids[q * k + (size_t)j]].c_str(),
+                   energy[q * k + (size_t)j], w.c_str());
+        }
+    kb2e_destroy(L.ctx);
+    return 0;
+}
+
 // classifyTransE|H|R: triple classification (Socher et al. 2013; TransH 4.3,
 // TransR 4.3) of the tables evalTrans* loads.  Per-relation thresholds are
 // fitted on the valid split and applied to the test split.  A split is either
@@ -1258,9 +1360,12 @@ int main(int argc, char** argv) {
     if (prog == "jointTransE") return joint_main(argc, argv, KB2E_TRANSE);
     if (prog == "jointTransH") return joint_main(argc, argv, KB2E_TRANSH);
     if (prog == "jointTransR") return joint_main(argc, argv, KB2E_TRANSR);
+    if (prog == "pathTransE") return path_main(argc, argv, KB2E_TRANSE);
+    if (prog == "pathTransH") return path_main(argc, argv, KB2E_TRANSH);
+    if (prog == "pathTransR") return path_main(argc, argv, KB2E_TRANSR);
     fprintf(stderr,
             "invoke as trainTransE|H|R, evalTransE|H|R, predictTransE|H|R, classifyTransE|H|R, completeTransE|H|R, "
-            "foldinTransE|H|R, foldrelTransE|H|R or jointTransE|H|R (got %s)\n",
+            "foldinTransE|H|R, foldrelTransE|H|R, jointTransE|H|R or pathTransE|H|R (got %s)\n",
             prog.c_str());
     return 2;
 }

@@ -37,7 +37,12 @@
 // Conjunctive queries (kb2e_predict_joint, kb2e_rank_joint: several one-sided
 // patterns about one unknown entity) score every pattern as a row with
 // predict_score_kernel, add a query's rows with joint_combine_kernel and share
-// the mask, the selection and the rank count (the last section of this file).
+// the mask, the selection and the rank count.
+//
+// Path queries (kb2e_predict_path, kb2e_rank_path: the entities at the end of a
+// relation path) score the first hop with predict_score_kernel, take every
+// further hop with the fused min-plus path_hop_kernel and share the mask, the
+// selection and the rank count (the last section of this file).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -53,6 +58,7 @@
 #include "hip_util.hpp"
 #include "joint_host.hpp"
 #include "kernels_common.hpp"
+#include "path_host.hpp"
 #include "predict.hpp"
 #include "predict_host.hpp"
 
@@ -1246,6 +1252,480 @@ void predict_joint(const EvalTables& t, const JointQuery& q, int32_t* ids, doubl
 void rank_joint(const EvalTables& t, const JointQuery& q, int64_t* ranks, JointStats* stats, const PredictHooks* hooks) {
     if (!q.truth) throw std::invalid_argument("rank_joint needs the true entities");
     run_joint(t, q, nullptr, nullptr, nullptr, ranks, stats, hooks);
+}
+
+// ------------------------------------------------------------ path queries
+//
+// Query q walks 1..8 hops from its anchor.  c_1[x] is the one-sided score row of
+// the anchor (predict_score_kernel, unchanged); hop i >= 2 is the min-plus step
+// c_i[y] = min over the frontier p of (c_{i-1}[p] + e_i(p, y)), which
+// path_hop_kernel computes without writing the |frontier| x |E| energies down.
+// The frontier is the whole previous key row (beam = 0) or its `beam` smallest
+// (cost, id) pairs, picked by predict_select_kernel on the unmasked row.  The
+// rows of the queries that end at a level are masked (the answers the filter's
+// paths already state, path_host.hpp), selected or ranked exactly as the joint
+// rows are.
+
+namespace {
+
+struct HopArgs {
+    const double* PT;    // [n][ne]
+    const double* relv;  // [n]
+    int32_t n, ne, l1, no_loops, eblocks;
+    int32_t stride;          // of fid / fcost rows: the beam, or ne for the identity frontier
+    const int32_t* slot;     // [slots] the chunk row of each query of this launch
+    const int32_t* sside;    // [slots] the hop's side: 1 walks head -> tail
+    const int32_t* fid;      // [rows][stride] frontier ids, or null: the identity list 0 .. ne - 1
+    const uint64_t* fcost;   // [rows][stride] their cumulative energies as bit patterns (~0: no path)
+    const int32_t* fcount;   // [rows] frontier entries, or null: ne
+    uint64_t* keys;          // [rows][ne] out: the bit pattern of the minimum (~0: no path)
+    int32_t* pred;           // [rows][ne] out: the frontier entity that gives it (-1: none)
+};
+
+// A flat grid: workgroup b takes targets (b % eblocks) * 256 .. of the launch's
+// query b / eblocks.  One thread per target y walks the query's frontier in
+// tiles of kQ rows: kQ serial FP64 sums in predict_score_kernel's operand order
+// (the hop energies, the bits of kb2e_score_triples), then per frontier row one
+// addition c[p] + e and a compare on (sum bits, predecessor id) -- the smallest
+// id wins among equal sums whatever order the frontier is walked in.  Dynamic
+// LDS (kRowsInLds): the tile's projected rows [kQ][n], r [n], the tile's costs
+// [kQ] and ids [kQ]; otherwise all of them are read from global memory at
+// workgroup-uniform addresses.
+template <bool kRowsInLds>
+__global__ __launch_bounds__(256) void path_hop_kernel(HopArgs a) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double* kr = lds;
+    double* rv = kr + kQ * a.n;
+    uint64_t* tcost = (uint64_t*)(rv + a.n);
+    int32_t* tid = (int32_t*)(tcost + kQ);
+    const int s = blockIdx.x / a.eblocks;
+    const int row = a.slot[s];
+    const bool tail = a.sside[s] != 0;
+    const int count = a.fcount ? a.fcount[row] : a.ne;
+    const int32_t* fid = a.fid ? a.fid + (int64_t)row * a.stride : nullptr;
+    const uint64_t* fcost = a.fcost + (int64_t)row * a.stride;
+    const int y = (blockIdx.x % a.eblocks) * blockDim.x + threadIdx.x;
+    const int yc = min(y, a.ne - 1);  // (the threads past |E| stay for the barriers and store nothing)
+    if constexpr (kRowsInLds)
+        for (int k = threadIdx.x; k < a.n; k += blockDim.x) rv[k] = a.relv[k];
+    uint64_t best = kMasked;
+    int32_t bestp = -1;
+    for (int t0 = 0; t0 < count; t0 += kQ) {  // (count is workgroup-uniform)
+        const int nt = min(kQ, count - t0);
+        if constexpr (kRowsInLds) {
+            __syncthreads();  // the last tile has been read
+            if ((int)threadIdx.x < kQ) {
+                const int q = threadIdx.x;
+                const int id = q < nt ? (fid ? fid[t0 + q] : t0 + q) : -1;
+                tid[q] = id;
+                tcost[q] = id >= 0 ? fcost[t0 + q] : kMasked;
+            }
+            for (int x = threadIdx.x; x < kQ * a.n; x += blockDim.x) {
+                const int q = x / a.n, k = x % a.n;
+                if (q < nt) {
+                    const int id = fid ? fid[t0 + q] : t0 + q;
+                    kr[x] = a.PT[(int64_t)k * a.ne + max(id, 0)];
+                }
+            }
+            __syncthreads();
+        }
+        int pid[kQ];  // (the L2 form's row addresses; the LDS form reads the ids where it needs them)
+#pragma unroll
+        for (int q = 0; q < kQ; ++q) pid[q] = kRowsInLds ? 0 : (q < nt ? (fid ? fid[t0 + q] : t0 + q) : -1);
+        double e[kQ];
+#pragma unroll
+        for (int q = 0; q < kQ; ++q) e[q] = 0;
+        for (int k = 0; k < a.n; ++k) {
+            const double* col = a.PT + (int64_t)k * a.ne;
+            const double v = col[yc];
+            const double r = kRowsInLds ? rv[k] : a.relv[k];
+#pragma unroll
+            for (int q = 0; q < kQ; ++q) {
+                const double p = kRowsInLds ? kr[q * a.n + k] : col[max(pid[q], 0)];
+                // (P(y) - P(p)) - r walking head -> tail, (P(p) - P(y)) - r backwards
+                const double d = tail ? v - p - r : p - v - r;
+                e[q] += a.l1 ? fabs(d) : d * d;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kQ; ++q) {
+            const int p = kRowsInLds ? tid[q] : pid[q];
+            const uint64_t cb = kRowsInLds ? tcost[q] : (p >= 0 ? fcost[t0 + q] : kMasked);
+            if (cb == kMasked || (a.no_loops && p == y)) continue;
+            const double sum = __longlong_as_double((long long)cb) + e[q];
+            const uint64_t sb = (uint64_t)__double_as_longlong(sum);
+            if (sb < best || (sb == best && p < bestp)) {
+                best = sb;
+                bestp = p;
+            }
+        }
+    }
+    if (y < a.ne) {
+        a.keys[(int64_t)row * a.ne + y] = best;
+        a.pred[(int64_t)row * a.ne + y] = bestp;
+    }
+}
+
+struct GatherArgs {
+    const int32_t* src;  // [rows][ne]
+    int32_t ne, m;
+    const int32_t* idx;  // [rows][m]
+    int32_t* out;        // [rows][m] = src[row][idx[row][j]], -1 where idx is
+};
+
+// One workgroup per row: the predecessors of the selected ids (a frontier's
+// back-pointers, the last step of the k answers, a step of the via chain).
+__global__ __launch_bounds__(256) void path_gather_kernel(GatherArgs a) {
+    const int32_t* src = a.src + (int64_t)blockIdx.x * a.ne;
+    const int32_t* idx = a.idx + (int64_t)blockIdx.x * a.m;
+    int32_t* out = a.out + (int64_t)blockIdx.x * a.m;
+    for (int j = threadIdx.x; j < a.m; j += blockDim.x) {
+        const int id = idx[j];
+        out[j] = id >= 0 && id < a.ne ? src[id] : -1;
+    }
+}
+
+// predict_path (ids / energy / found / via) when q.truth is null, else rank_path (ranks).
+void run_path(const EvalTables& t, const PathQuery& q, int32_t* ids, double* energy, int32_t* found, int32_t* via,
+              int64_t* ranks, PathStats* stats, const PredictHooks* hooks) {
+    const int ne = t.ne, n = t.n, k = q.k;
+    const bool ranking = q.truth != nullptr;
+    if (q.nq < 1) throw std::invalid_argument("no queries");
+    if (q.nq > INT32_MAX) throw std::invalid_argument("too many queries in one call");
+    if (!ranking && (k < 1 || k > kPredictMaxK))
+        throw std::invalid_argument("k must be in 1.." + std::to_string(kPredictMaxK));
+    if (q.beam < 0 || q.beam > kPathMaxBeam) throw std::invalid_argument("beam must be in 0..1024");
+    if (q.no_loops != 0 && q.no_loops != 1) throw std::invalid_argument("no_loops must be 0 or 1");
+    if (const char* why = path_check_offsets(q.offsets, q.nq)) throw std::invalid_argument(why);
+    const int64_t nq = q.nq, nhops = q.offsets[nq];
+    for (int64_t c = 0; c < nhops; ++c) {
+        if (q.side[c] != 0 && q.side[c] != 1) throw std::invalid_argument("hop side must be 0 (backwards) or 1");
+        if (q.rel[c] < 0 || q.rel[c] >= t.nr) throw std::invalid_argument("hop " + std::to_string(c) + " has a relation out of range");
+    }
+    for (int64_t x = 0; x < nq; ++x) {
+        if (q.anchors[x] < 0 || q.anchors[x] >= ne)
+            throw std::invalid_argument("query " + std::to_string(x) + " has an anchor out of range");
+        if (ranking && (q.truth[x] < 0 || q.truth[x] >= ne))
+            throw std::invalid_argument("query " + std::to_string(x) + " has a truth out of range");
+    }
+    for (int64_t x = 0; x < q.nfilter; ++x)
+        if (q.fh[x] < 0 || q.fh[x] >= ne || q.ft[x] < 0 || q.ft[x] >= ne || q.fr[x] < 0 || q.fr[x] >= t.nr)
+            throw std::invalid_argument("filter triple out of range");
+
+    const bool exact = q.beam == 0, no_loops = q.no_loops != 0, want_via = !ranking && via != nullptr;
+    const int32_t B = exact ? 0 : std::min<int32_t>(q.beam, ne);  // (a frontier holds no more than |E|)
+    int maxL = 1;
+    for (int64_t x = 0; x < nq; ++x) maxL = std::max(maxL, (int)(q.offsets[x + 1] - q.offsets[x]));
+    if (want_via) std::fill(via, via + nq * (int64_t)k * (kPathMaxHops - 1), -1);
+
+    // excluded per query: the ends of the filter's own paths
+    const PathKnown pk = path_known_answers(q.anchors, q.offsets, q.rel, q.side, nq, no_loops, q.fh, q.ft, q.fr,
+                                            q.nfilter, t.nr);
+
+    // the |E|-long rows of a chunk: <= 1 GiB, counted in rows of |E| 4-byte words
+    // (KB2E_PATH_CHUNK_ROWS lowers that: tests); the short per-query buffers
+    // (frontiers, back-pointers, answers) of a chunk: <= 256 MiB
+    int64_t budget = std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)ne * 4));
+    if (const long v = env_long("KB2E_PATH_CHUNK_ROWS"); v >= 1) budget = std::min<int64_t>(budget, v);
+    const int64_t small = (int64_t)(maxL - 1) * B * 8 + (int64_t)B * 12 + 64 +
+                          (ranking ? 16 : (int64_t)k * (12 + 4 * (kPathMaxHops - 1)));
+    const std::vector<PathChunk> chunks = path_plan_chunks(q.offsets, nq, exact, budget, ((int64_t)256 << 20) / small);
+    int64_t maxq = 0, maxlive2 = 0, maxpred = 0;  // rows of the largest chunk; with >= 2 hops; back-pointer rows
+    for (const PathChunk& ch : chunks) {
+        int64_t live2 = 0, prows = 0;
+        for (int64_t x = ch.q0; x < ch.q1; ++x) {
+            const int64_t L = q.offsets[x + 1] - q.offsets[x];
+            live2 += L >= 2;
+            prows += exact ? L - 1 : (L >= 2);
+        }
+        maxq = std::max(maxq, ch.q1 - ch.q0);
+        maxlive2 = std::max(maxlive2, live2);
+        maxpred = std::max(maxpred, prows);
+    }
+
+    // the score, hop and selection forms: predict_topk's rules
+    const bool l2 = env_on("KB2E_EVAL_ROWS_L2");
+    const bool rows_lds = (size_t)(kQ + 1) * n * 8 <= kLdsMax && !l2;
+    const size_t score_lds = rows_lds ? (size_t)(kQ + 1) * n * 8 : 0;
+    const size_t hop_bytes = (size_t)(kQ + 1) * n * 8 + (size_t)kQ * 12;
+    const bool hop_rows_lds = hop_bytes <= kLdsMax && !l2;
+    const size_t hop_lds = hop_rows_lds ? hop_bytes : 0;
+    const size_t staged = kSelScratchBytes + (size_t)ne * 8;
+    const char* kl2 = getenv("KB2E_PREDICT_KEYS_L2");
+    bool keys_lds = staged <= kLdsMax / 4;
+    if (kl2 && kl2[0] == '1') keys_lds = false;
+    if (kl2 && kl2[0] == '0') keys_lds = staged <= kLdsMax;
+    const size_t select_lds = kSelScratchBytes + (keys_lds ? (size_t)ne * 8 : 0);
+    if (rows_lds) allow_lds(predict_score_kernel<true>, score_lds);
+    if (hop_rows_lds && maxL >= 2) allow_lds(path_hop_kernel<true>, hop_lds);
+    if (keys_lds) allow_lds(predict_select_kernel<true>, select_lds);
+
+    DevBuf d_anchor, d_side1, d_iota, d_iota64, d_g, d_off, d_kid, d_truth, d_slot, d_sside, d_keys0, d_keys1, d_pred,
+        d_fid, d_back, d_fcost, d_fcount, d_ids, d_en, d_found, d_last, d_via, d_ranks, d_PT, d_relv;
+    d_anchor.alloc((size_t)maxq * 4);
+    d_side1.alloc((size_t)maxq * 4);
+    d_g.alloc((size_t)maxq * 4);
+    d_off.alloc(pk.off.size() * 8);
+    d_kid.alloc(pk.ids.size() * 4);
+    HIPCHK(hipMemcpyAsync(d_off.p, pk.off.data(), pk.off.size() * 8, hipMemcpyHostToDevice, t.stream));
+    if (!pk.ids.empty())
+        HIPCHK(hipMemcpyAsync(d_kid.p, pk.ids.data(), pk.ids.size() * 4, hipMemcpyHostToDevice, t.stream));
+    std::vector<int32_t> iota;
+    std::vector<int64_t> iota64;
+    if (no_loops) {  // hop 1 leaves out x_1 == the anchor: one masked key per row
+        iota.resize((size_t)maxq), iota64.resize((size_t)maxq + 1);
+        std::iota(iota.begin(), iota.end(), 0);
+        std::iota(iota64.begin(), iota64.end(), (int64_t)0);
+        d_iota.alloc((size_t)maxq * 4);
+        d_iota64.alloc((size_t)(maxq + 1) * 8);
+        HIPCHK(hipMemcpyAsync(d_iota.p, iota.data(), (size_t)maxq * 4, hipMemcpyHostToDevice, t.stream));
+        HIPCHK(hipMemcpyAsync(d_iota64.p, iota64.data(), (size_t)(maxq + 1) * 8, hipMemcpyHostToDevice, t.stream));
+    }
+    if (ranking) {
+        d_truth.alloc((size_t)maxq * 4);
+        d_ranks.alloc((size_t)maxq * 2 * 8);
+    } else {
+        d_ids.alloc((size_t)maxq * k * 4);
+        d_en.alloc((size_t)maxq * k * 8);
+        d_found.alloc((size_t)maxq * 4);
+    }
+    d_keys0.alloc((size_t)maxq * ne * 8);
+    if (maxlive2 > 0) {
+        d_slot.alloc((size_t)(maxL - 1) * maxlive2 * 4);
+        d_sside.alloc((size_t)(maxL - 1) * maxlive2 * 4);
+        d_pred.alloc((size_t)maxpred * ne * 4);
+        if (exact) {
+            d_keys1.alloc((size_t)maxlive2 * ne * 8);
+            if (want_via) d_via.alloc((size_t)(maxL - 1) * maxlive2 * k * 4);
+        } else {
+            d_fid.alloc((size_t)(maxL - 1) * maxlive2 * B * 4);
+            d_fcost.alloc((size_t)maxlive2 * B * 8);
+            d_fcount.alloc((size_t)maxlive2 * 4);
+            if (want_via) {
+                d_back.alloc((size_t)(maxL - 1) * maxlive2 * B * 4);
+                d_last.alloc((size_t)maxlive2 * k * 4);
+            }
+        }
+    }
+    d_PT.alloc((size_t)n * ne * 8);
+    d_relv.alloc((size_t)n * 8);
+
+    const int32_t eblocks = (ne + 255) / 256;
+    const int64_t fstride = maxlive2 * B;  // of one level in d_fid / d_back
+    // (the chunk's host arrays live until its synchronise: their copies are queued)
+    std::vector<int32_t> h_anchor, h_side1, h_g, h_truth, hids, hfound, hlast, hvia, hfid, hback;
+    std::vector<double> hen;
+    std::vector<int64_t> hranks;
+    std::vector<PathLevel> levels;
+    int cur_rel = -1;  // the relation d_PT holds (kept across levels and chunks)
+    auto project_once = [&](int r) {
+        if (r == cur_rel) return;
+        Span sp(hooks, "path_score");
+        project_any(t, r, d_PT.as<double>(), d_relv.as<double>());
+        sp.end();
+        cur_rel = r;
+        if (stats) ++stats->projections;
+    };
+    auto gather = [&](const int32_t* src, const int32_t* idx, int32_t m, int32_t* out, int64_t rows) {
+        path_gather_kernel<<<(unsigned)rows, 256, 0, t.stream>>>(GatherArgs{src, ne, m, idx, out});
+        HIPCHK(hipGetLastError());
+    };
+    for (const PathChunk& ch : chunks) {
+        const std::vector<int64_t> order = path_chunk_order(q.offsets, q.rel, q.side, ch.q0, ch.q1);
+        const int64_t mq = ch.q1 - ch.q0;
+        int64_t live[kPathMaxHops + 2], lvl_off[kPathMaxHops + 2];  // rows with >= i hops; exact: level i's first pred row
+        for (int i = 1; i <= kPathMaxHops + 1; ++i) live[i] = path_live(q.offsets, order, i);
+        lvl_off[2] = 0;
+        for (int i = 3; i <= kPathMaxHops + 1; ++i) lvl_off[i] = lvl_off[i - 1] + (exact ? live[i - 1] : 0);
+        h_anchor.resize((size_t)mq), h_side1.resize((size_t)mq), h_g.resize((size_t)mq);
+        for (int64_t x = 0; x < mq; ++x) {
+            const int64_t o = order[(size_t)x];
+            h_anchor[(size_t)x] = q.anchors[o];
+            h_side1[(size_t)x] = q.side[q.offsets[o]];
+            h_g[(size_t)x] = (int32_t)o;
+        }
+        HIPCHK(hipMemcpyAsync(d_anchor.p, h_anchor.data(), (size_t)mq * 4, hipMemcpyHostToDevice, t.stream));
+        HIPCHK(hipMemcpyAsync(d_side1.p, h_side1.data(), (size_t)mq * 4, hipMemcpyHostToDevice, t.stream));
+        HIPCHK(hipMemcpyAsync(d_g.p, h_g.data(), (size_t)mq * 4, hipMemcpyHostToDevice, t.stream));
+        if (ranking) {
+            h_truth.resize((size_t)mq);
+            for (int64_t x = 0; x < mq; ++x) h_truth[(size_t)x] = q.truth[order[(size_t)x]];
+            HIPCHK(hipMemcpyAsync(d_truth.p, h_truth.data(), (size_t)mq * 4, hipMemcpyHostToDevice, t.stream));
+        }
+        levels.clear();
+        levels.reserve(kPathMaxHops);  // (no reallocation: the copies of a level's arrays are queued)
+        int chunkL = 1;
+        while (chunkL < kPathMaxHops && live[chunkL + 1] > 0) ++chunkL;
+        for (int i = 1; i <= chunkL; ++i) {
+            levels.push_back(path_plan_level(q.offsets, q.rel, q.side, order, i));
+            const PathLevel& pl = levels.back();
+            const int64_t m = live[i];
+            // hop i writes this buffer; the exact form reads the other one as the frontier's costs
+            uint64_t* kout = (exact && (i & 1) == 0 ? d_keys1 : d_keys0).as<uint64_t>();
+            if (i == 1) {
+                // the rows of a (relation, side) are consecutive inside one length class: one launch per such run
+                for (int64_t a0 = 0; a0 < m;) {
+                    const int r = pl.rel[(size_t)a0];
+                    int64_t a1 = a0 + 1;
+                    while (a1 < m && pl.rel[(size_t)a1] == r && pl.row[(size_t)a1] == pl.row[(size_t)a1 - 1] + 1 &&
+                           a1 - a0 < kScoreMaxRows)
+                        ++a1;
+                    project_once(r);
+                    const int64_t r0 = pl.row[(size_t)a0];
+                    Span sp(hooks, "path_score");
+                    ScoreArgs sa{d_PT.as<double>(), d_relv.as<double>(), n, ne, t.l1, d_anchor.as<int32_t>() + r0,
+                                 d_side1.as<int32_t>() + r0, (int32_t)(a1 - a0), kout + r0 * ne};
+                    dim3 grid((unsigned)eblocks, (unsigned)((a1 - a0 + kQ - 1) / kQ));
+                    if (rows_lds) predict_score_kernel<true><<<grid, 256, score_lds, t.stream>>>(sa);
+                    else predict_score_kernel<false><<<grid, 256, 0, t.stream>>>(sa);
+                    HIPCHK(hipGetLastError());
+                    sp.end();
+                    a0 = a1;
+                }
+                if (no_loops) {
+                    Span sp(hooks, "path_mask");
+                    MaskArgs ma{kout, ne, d_iota.as<int32_t>(), d_iota64.as<int64_t>(), d_anchor.as<int32_t>()};
+                    predict_mask_kernel<<<(unsigned)mq, 256, 0, t.stream>>>(ma);
+                    HIPCHK(hipGetLastError());
+                    sp.end();
+                }
+            } else {
+                int32_t* dslot = d_slot.as<int32_t>() + (int64_t)(i - 2) * maxlive2;
+                int32_t* dside = d_sside.as<int32_t>() + (int64_t)(i - 2) * maxlive2;
+                HIPCHK(hipMemcpyAsync(dslot, pl.row.data(), (size_t)m * 4, hipMemcpyHostToDevice, t.stream));
+                HIPCHK(hipMemcpyAsync(dside, pl.side.data(), (size_t)m * 4, hipMemcpyHostToDevice, t.stream));
+                for (int64_t a0 = 0; a0 < m;) {
+                    const int r = pl.rel[(size_t)a0];
+                    int64_t a1 = a0;
+                    while (a1 < m && pl.rel[(size_t)a1] == r) ++a1;
+                    project_once(r);
+                    Span sp(hooks, "path_hop");
+                    HopArgs ha{d_PT.as<double>(), d_relv.as<double>(), n, ne, t.l1, no_loops ? 1 : 0, eblocks,
+                               exact ? ne : B, dslot + a0, dside + a0,
+                               exact ? nullptr : d_fid.as<int32_t>() + (int64_t)(i - 2) * fstride,
+                               exact ? ((i & 1) == 0 ? d_keys0 : d_keys1).as<uint64_t>() : d_fcost.as<uint64_t>(),
+                               exact ? nullptr : d_fcount.as<int32_t>(), kout,
+                               d_pred.as<int32_t>() + lvl_off[i] * ne};
+                    const unsigned blocks = (unsigned)((a1 - a0) * eblocks);
+                    if (hop_rows_lds) path_hop_kernel<true><<<blocks, 256, hop_lds, t.stream>>>(ha);
+                    else path_hop_kernel<false><<<blocks, 256, 0, t.stream>>>(ha);
+                    HIPCHK(hipGetLastError());
+                    sp.end();
+                    a0 = a1;
+                }
+                if (stats) stats->hops += m;
+            }
+            const int32_t* pred_i = i >= 2 ? d_pred.as<int32_t>() + lvl_off[i] * ne : nullptr;
+            // the queries that end here: rows [live[i + 1], live[i])
+            const int64_t f0 = live[i + 1], nf = live[i] - f0;
+            if (nf > 0 && ranking) {
+                Span sp(hooks, "path_rank");
+                RelRankArgs ra{kout + f0 * ne, ne, d_truth.as<int32_t>() + f0, d_g.as<int32_t>() + f0,
+                               d_off.as<int64_t>(), d_kid.as<int32_t>(), d_ranks.as<int64_t>() + f0 * 2};
+                relpred_rank_kernel<<<(unsigned)nf, 256, 0, t.stream>>>(ra);
+                HIPCHK(hipGetLastError());
+                sp.end();
+            } else if (nf > 0) {
+                if (!pk.ids.empty()) {
+                    Span sp(hooks, "path_mask");
+                    MaskArgs ma{kout + f0 * ne, ne, d_g.as<int32_t>() + f0, d_off.as<int64_t>(), d_kid.as<int32_t>()};
+                    predict_mask_kernel<<<(unsigned)nf, 256, 0, t.stream>>>(ma);
+                    HIPCHK(hipGetLastError());
+                    sp.end();
+                }
+                Span sp(hooks, "path_select");
+                SelectArgs sa{kout + f0 * ne, ne, k, d_ids.as<int32_t>() + f0 * k, d_en.as<double>() + f0 * k,
+                              d_found.as<int32_t>() + f0};
+                if (keys_lds) predict_select_kernel<true><<<(unsigned)nf, kSelThreads, select_lds, t.stream>>>(sa);
+                else predict_select_kernel<false><<<(unsigned)nf, kSelThreads, select_lds, t.stream>>>(sa);
+                HIPCHK(hipGetLastError());
+                if (want_via && i >= 2) {
+                    if (exact) {
+                        // x_{i-1} of the answers, then x_{i-2} of those, ...: each level's back-pointer rows are kept
+                        const int32_t* cur = d_ids.as<int32_t>() + f0 * k;
+                        for (int lev = i; lev >= 2; --lev) {
+                            int32_t* out = d_via.as<int32_t>() + ((int64_t)(lev - 2) * maxlive2 + f0) * k;
+                            gather(d_pred.as<int32_t>() + (lvl_off[lev] + f0) * ne, cur, k, out, nf);
+                            cur = out;
+                        }
+                    } else {
+                        gather(pred_i + f0 * ne, d_ids.as<int32_t>() + f0 * k, k, d_last.as<int32_t>() + f0 * k, nf);
+                    }
+                }
+                sp.end();
+            }
+            // the frontier of the queries that walk on: rows [0, live[i + 1])
+            if (!exact && f0 > 0) {
+                Span sp(hooks, "path_select");
+                int32_t* fid_i = d_fid.as<int32_t>() + (int64_t)(i - 1) * fstride;
+                SelectArgs sa{kout, ne, B, fid_i, d_fcost.as<double>(), d_fcount.as<int32_t>()};
+                if (keys_lds) predict_select_kernel<true><<<(unsigned)f0, kSelThreads, select_lds, t.stream>>>(sa);
+                else predict_select_kernel<false><<<(unsigned)f0, kSelThreads, select_lds, t.stream>>>(sa);
+                HIPCHK(hipGetLastError());
+                if (want_via && i >= 2) gather(pred_i, fid_i, B, d_back.as<int32_t>() + (int64_t)(i - 1) * fstride, f0);
+                sp.end();
+            }
+        }
+        // only the answers, and for their witnesses the frontiers' ids and back-pointers, leave the card
+        const int64_t l2rows = live[2];
+        if (ranking) {
+            hranks.resize((size_t)mq * 2);
+            HIPCHK(hipMemcpyAsync(hranks.data(), d_ranks.p, (size_t)mq * 2 * 8, hipMemcpyDeviceToHost, t.stream));
+        } else {
+            hids.resize((size_t)mq * k), hen.resize((size_t)mq * k), hfound.resize((size_t)mq);
+            HIPCHK(hipMemcpyAsync(hids.data(), d_ids.p, (size_t)mq * k * 4, hipMemcpyDeviceToHost, t.stream));
+            HIPCHK(hipMemcpyAsync(hen.data(), d_en.p, (size_t)mq * k * 8, hipMemcpyDeviceToHost, t.stream));
+            HIPCHK(hipMemcpyAsync(hfound.data(), d_found.p, (size_t)mq * 4, hipMemcpyDeviceToHost, t.stream));
+            if (want_via && l2rows > 0) {
+                if (exact) {
+                    hvia.resize((size_t)(chunkL - 1) * maxlive2 * k);
+                    HIPCHK(hipMemcpyAsync(hvia.data(), d_via.p, hvia.size() * 4, hipMemcpyDeviceToHost, t.stream));
+                } else {
+                    hfid.resize((size_t)(chunkL - 1) * fstride), hback.resize(hfid.size()), hlast.resize((size_t)l2rows * k);
+                    HIPCHK(hipMemcpyAsync(hfid.data(), d_fid.p, hfid.size() * 4, hipMemcpyDeviceToHost, t.stream));
+                    HIPCHK(hipMemcpyAsync(hback.data(), d_back.p, hback.size() * 4, hipMemcpyDeviceToHost, t.stream));
+                    HIPCHK(hipMemcpyAsync(hlast.data(), d_last.p, hlast.size() * 4, hipMemcpyDeviceToHost, t.stream));
+                }
+            }
+        }
+        HIPCHK(hipStreamSynchronize(t.stream));
+        for (int64_t x = 0; x < mq; ++x) {  // back to the caller's order
+            const int64_t o = order[(size_t)x];
+            if (ranking) {
+                ranks[o * 2] = hranks[(size_t)x * 2];
+                ranks[o * 2 + 1] = hranks[(size_t)x * 2 + 1];
+                continue;
+            }
+            std::copy_n(hids.data() + x * k, k, ids + o * k);
+            std::copy_n(hen.data() + x * k, k, energy + o * k);
+            found[o] = hfound[(size_t)x];
+            const int L = (int)(q.offsets[o + 1] - q.offsets[o]);
+            if (!want_via || L < 2) continue;
+            for (int j = 0; j < hfound[(size_t)x]; ++j) {
+                int32_t* w = via + (o * k + j) * (kPathMaxHops - 1);
+                if (exact) {
+                    for (int lev = 2; lev <= L; ++lev) w[lev - 2] = hvia[(size_t)(((int64_t)(lev - 2) * maxlive2 + x) * k + j)];
+                } else if (!path_backtrack(L, B, hfid.data() + x * B, hback.data() + x * B, fstride,
+                                           hlast[(size_t)(x * k + j)], w)) {
+                    throw std::runtime_error("path query: a predecessor outside its frontier");
+                }
+            }
+        }
+        if (stats) ++stats->chunks;
+    }
+}
+
+}  // namespace
+
+void predict_path(const EvalTables& t, const PathQuery& q, int32_t* ids, double* energy, int32_t* found, int32_t* via,
+                  PathStats* stats, const PredictHooks* hooks) {
+    if (q.truth) throw std::invalid_argument("predict_path takes no true entities");
+    run_path(t, q, ids, energy, found, via, nullptr, stats, hooks);
+}
+
+void rank_path(const EvalTables& t, const PathQuery& q, int64_t* ranks, PathStats* stats, const PredictHooks* hooks) {
+    if (!q.truth) throw std::invalid_argument("rank_path needs the true entities");
+    run_path(t, q, nullptr, nullptr, nullptr, nullptr, ranks, stats, hooks);
 }
 
 }  // namespace kb2e

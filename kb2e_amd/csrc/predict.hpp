@@ -114,4 +114,38 @@ void predict_joint(const EvalTables& t, const JointQuery& q, int32_t* ids, doubl
 void rank_joint(const EvalTables& t, const JointQuery& q, int64_t* ranks, JointStats* stats = nullptr,
                 const PredictHooks* hooks = nullptr);
 
+// Path queries: query q starts at anchors[q] and owns the hops offsets[q] ..
+// offsets[q + 1] - 1 (1..8 of them), each (rel, side) as PredictQuery's: side 1
+// steps from the head to the tail of the relation, side 0 backwards.  The path
+// energy of an entity is the smallest sum of hop energies, added in hop order,
+// over the paths that end in it; after every hop but the last only the `beam`
+// entities of smallest (energy, id) are kept (0: all of them).
+struct PathQuery {
+    const int32_t* anchors;      // [nq]
+    const int64_t* offsets;      // [nq + 1]
+    const int32_t *rel, *side;   // [offsets[nq]]
+    const int32_t* truth;        // rank_path: the entity to rank per query (else null)
+    int64_t nq;
+    int32_t k;                   // predict_path: 1..kPredictMaxK
+    int32_t beam, no_loops;      // 0..1024; 0 / 1
+    const int32_t *fh, *ft, *fr;
+    int64_t nfilter;
+};
+
+// The last call's numbers (kb2e_counter "path_*").
+struct PathStats {
+    int64_t chunks = 0;       // runs of queries that shared the device rows
+    int64_t hops = 0;         // query-levels the hop kernel ran (hops 2..L of every query)
+    int64_t projections = 0;  // project_any calls
+};
+
+// ids / energy [nq][k], found [nq]: as predict_topk, on the path energies; via
+// [nq][k][7] (or null): the intermediate entities of each answer's winning path.
+void predict_path(const EvalTables& t, const PathQuery& q, int32_t* ids, double* energy, int32_t* found, int32_t* via,
+                  PathStats* stats = nullptr, const PredictHooks* hooks = nullptr);
+
+// ranks[q * 2 + 0..1] = raw and filtered rank of truth[q] among the |E| candidates of query q.
+void rank_path(const EvalTables& t, const PathQuery& q, int64_t* ranks, PathStats* stats = nullptr,
+               const PredictHooks* hooks = nullptr);
+
 }  // namespace kb2e

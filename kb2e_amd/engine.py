@@ -31,9 +31,10 @@ EXPORTS = [
     "kb2e_merge_epoch_group", "kb2e_comm_info", "kb2e_get_config", "kb2e_score_triples", "kb2e_predict",
     "kb2e_rank_triples", "kb2e_predict_relations", "kb2e_rank_relations", "kb2e_fit_thresholds",
     "kb2e_classify_triples", "kb2e_corrupt_triples", "kb2e_complete_triples", "kb2e_fold_in_entities",
-    "kb2e_fold_in_relations", "kb2e_predict_joint", "kb2e_rank_joint",
+    "kb2e_fold_in_relations", "kb2e_predict_joint", "kb2e_rank_joint", "kb2e_predict_path", "kb2e_rank_path",
 ]
 COMM_ID_BYTES = 128
+PATH_MAX_HOPS = 8  # KB2E_PATH_MAX_HOPS
 READ_VERBATIM, READ_UNIT, READ_SHRINK = 0, 1, 2
 
 
@@ -101,6 +102,10 @@ def lib():
                                          i32p]),
             "kb2e_rank_joint": (i32, [vp, C.POINTER(i64), i32p, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64,
                                       C.POINTER(i64)]),
+            "kb2e_predict_path": (i32, [vp, i32p, C.POINTER(i64), i32p, i32p, i64, i32, i32, i32, i32p, i32p, i32p, i64,
+                                        i32p, dp, i32p, i32p]),
+            "kb2e_rank_path": (i32, [vp, i32p, C.POINTER(i64), i32p, i32p, i32p, i64, i32, i32, i32p, i32p, i32p, i64,
+                                     C.POINTER(i64)]),
             "kb2e_fit_thresholds": (i32, [vp, i32p, i32p, i32p, u8p, i64, dp, C.POINTER(i64), dp, C.POINTER(i64)]),
             "kb2e_classify_triples": (i32, [vp, i32p, i32p, i32p, i64, dp, u8p, dp]),
             "kb2e_corrupt_triples": (i32, [vp, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, C.c_uint64, i32, i32,
@@ -496,6 +501,64 @@ class Engine:
                                           _ip(cols[1]), _ip(cols[2]), _ip(tr), nq,
                                           *[None if c is None else _ip(c) for c in fc], nf,
                                           ranks.ctypes.data_as(C.POINTER(C.c_int64))), "rank_joint")
+        return ranks
+
+    # ------------------------------------------------ path queries
+    @staticmethod
+    def _path_arrays(anchors, paths):
+        """anchors int32[nq], offsets int64[nq + 1] and the (relation, side) columns
+        of the paths' hops, concatenated in order."""
+        an = np.ascontiguousarray(anchors, dtype=np.int32).reshape(-1)
+        hops = [np.ascontiguousarray(p, dtype=np.int32).reshape(-1, 2) for p in paths]
+        if len(hops) != len(an):
+            raise ValueError("anchors and paths differ in length")
+        offsets = np.zeros(len(hops) + 1, np.int64)
+        if hops:
+            offsets[1:] = np.cumsum([len(h) for h in hops])
+        cat = np.concatenate(hops + [np.zeros((0, 2), np.int32)])
+        return an, offsets, np.ascontiguousarray(cat[:, 0]), np.ascontiguousarray(cat[:, 1])
+
+    def predict_path(self, anchors, paths, k, filt=None, *, beam=0, no_loops=False, via=False):
+        """Top-k entities at the end of a relation path.  Query q starts at
+        anchors[q] and walks paths[q] = [[relation, side], ...], 1..8 hops in
+        predict()'s convention (side 1: head -> tail, side 0: backwards).  An
+        answer's energy is the smallest sum of hop energies, added in hop order,
+        over the paths that end in it; after every hop but the last only the
+        `beam` entities of smallest (energy, id) are walked on (0: all, the exact
+        minimum).  no_loops: a hop may not stay on its entity.  An answer is
+        excluded iff the rows of `filt` themselves lead to it along the path.
+        Returns (ids int32[nq, k], energy float64[nq, k], found int32[nq]) as
+        predict(); with via=True also int32[nq, k, 7], the intermediate entities
+        of each answer's winning path, -1 behind."""
+        an, offsets, rel, side = self._path_arrays(anchors, paths)
+        nq, k = len(an), int(k)
+        fc, nf = self._filter_cols(filt)
+        kk = max(k, 1)
+        ids = np.full((nq, kk), -1, np.int32)
+        en = np.full((nq, kk), np.inf)
+        found = np.zeros(nq, np.int32)
+        w = np.full((nq, kk, PATH_MAX_HOPS - 1), -1, np.int32) if via else None
+        self._check(lib().kb2e_predict_path(self.h, _ip(an), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ip(rel),
+                                            _ip(side), nq, k, int(beam), int(no_loops),
+                                            *[None if c is None else _ip(c) for c in fc], nf, _ip(ids), _dp(en),
+                                            _ip(found), None if w is None else _ip(w)), "predict_path")
+        return (ids, en, found, w) if via else (ids, en, found)
+
+    def rank_path(self, anchors, paths, truth, filt=None, *, beam=0, no_loops=False):
+        """The rank of truth[q] among all entities by the path energy of query q
+        (predict_path's queries), in the caller's order: int64[nq, 2] = raw, and
+        with the excluded candidates other than the truth left out."""
+        an, offsets, rel, side = self._path_arrays(anchors, paths)
+        nq = len(an)
+        tr = np.ascontiguousarray(truth, dtype=np.int32).reshape(-1)
+        if len(tr) != nq:
+            raise ValueError("queries and truth differ in length")
+        fc, nf = self._filter_cols(filt)
+        ranks = np.zeros((nq, 2), np.int64)
+        self._check(lib().kb2e_rank_path(self.h, _ip(an), offsets.ctypes.data_as(C.POINTER(C.c_int64)), _ip(rel),
+                                         _ip(side), _ip(tr), nq, int(beam), int(no_loops),
+                                         *[None if c is None else _ip(c) for c in fc], nf,
+                                         ranks.ctypes.data_as(C.POINTER(C.c_int64))), "rank_path")
         return ranks
 
     # ------------------------------------------------ triple classification

@@ -32,6 +32,8 @@ trained model frozen, and their remaining triples are ranked before and after.
 ``entity_identification`` is its counterpart for entities the model has: the
 test triples that mention an entity, with the entity taken out, are one
 conjunctive query (``Engine.rank_joint``) that should rank it first.
+``path_evaluation`` ranks the tail of every test triple at the end of a relation
+path that reaches its head through train triples (``Engine.rank_path``).
 """
 from __future__ import annotations
 
@@ -478,4 +480,72 @@ def entity_identification(eng, ds, constraints=(1, 2, 3)):
     for m in constraints:
         ranks = np.asarray(eng.rank_joint([p[:m] for p in patterns], ents, filt)).reshape(-1, 2)
         out[m] = {"count": int(len(ents)), "raw": rank_metrics(ranks[:, 0]), "filtered": rank_metrics(ranks[:, 1])}
+    return out
+
+
+def path_query_set(ds, hops, seed=0):
+    """Path queries whose last hop is a test triple.  For every row (h, t, r) of
+    ``ds.test``, in order, walk ``hops - 1`` steps backwards from h through
+    ``ds.train``: at entity e one of the train triples that mention e, in either
+    role, is chosen uniformly (``numpy.random.default_rng(seed)``, one draw per
+    step, over the triples in file order); (a, e, r') is the forward hop
+    (r', 1) from a, (e, b, r') the hop (r', 0) -- r' walked backwards -- from b.
+    A test triple whose walk meets an entity no train triple mentions is
+    dropped.  Returns (anchors int32[nq], paths list of int32[hops, 2] rows of
+    (relation, side), truth int32[nq]): the walk's last entity, the hops from
+    it to h followed by (r, 1), and t."""
+    hops = int(hops)
+    if hops < 1:
+        raise ValueError("hops must be positive")
+    train = np.asarray(ds.train, dtype=np.int64).reshape(-1, 3)
+    mentions = {}
+    if hops > 1:
+        for i, (h, t, _) in enumerate(train.tolist()):
+            mentions.setdefault(h, []).append(i)
+            if t != h:
+                mentions.setdefault(t, []).append(i)
+    rng = np.random.default_rng(seed)
+    anchors, paths, truth = [], [], []
+    for h, t, r in np.asarray(ds.test, dtype=np.int64).reshape(-1, 3).tolist():
+        at, back = h, []
+        for _ in range(hops - 1):
+            cand = mentions.get(at)
+            if not cand:
+                back = None
+                break
+            a, b, rr = train[cand[int(rng.integers(len(cand)))]].tolist()
+            if b == at:  # (a, at, rr): forwards from a
+                back.append((rr, 1))
+                at = a
+            else:        # (at, b, rr): backwards from b
+                back.append((rr, 0))
+                at = b
+        if back is None:
+            continue
+        anchors.append(at)
+        paths.append(np.array(back[::-1] + [(r, 1)], np.int32).reshape(-1, 2))
+        truth.append(t)
+    return np.array(anchors, np.int32), paths, np.array(truth, np.int32)
+
+
+def path_evaluation(eng, ds, hops=(1, 2, 3), beam=64, seed=0, limit=None):
+    """Link prediction at the end of a path: for each length of `hops` the queries
+    of ``path_query_set`` (the first `limit` of them, if given) are ranked by
+    ``Engine.rank_path`` with the given beam (0: exact) and filter = train +
+    valid + test.  Returns {length: {"count",
+    "raw": {...}, "filtered": {...}}} with mean rank, MRR, Hits@1 and Hits@10
+    (``rank_metrics``)."""
+    hops = tuple(int(m) for m in hops)
+    if not hops or min(hops) < 1:
+        raise ValueError("hops must be positive")
+    filt = np.concatenate([ds.train, ds.valid, ds.test]).astype(np.int32)
+    out = {}
+    for m in hops:
+        anchors, paths, truth = path_query_set(ds, m, seed)
+        if limit is not None:
+            anchors, paths, truth = anchors[:limit], paths[:limit], truth[:limit]
+        if len(anchors) == 0:
+            raise ValueError("no test triple has a path of %d hops" % m)
+        ranks = np.asarray(eng.rank_path(anchors, paths, truth, filt, beam=beam)).reshape(-1, 2)
+        out[m] = {"count": int(len(anchors)), "raw": rank_metrics(ranks[:, 0]), "filtered": rank_metrics(ranks[:, 1])}
     return out
