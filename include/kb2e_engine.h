@@ -202,7 +202,9 @@ kb2e_status kb2e_take_stats(kb2e_ctx* ctx, double* loss, int64_t* active);
  * uses the zeroed (fixed) work vectors here; kb2e_evaluate_transr_compat is
  * the reference evalTransR's stateful energy.  Every dim a context takes
  * (kb2e_create: <= 512); the ranking itself has no limit (the query rows of a
- * rank tile are staged in LDS up to dim 600, read from L2 above). */
+ * rank tile are staged in LDS up to dim 600, read from L2 above).
+ * KB2E_EINVAL (here and in kb2e_evaluate_transr_compat): ntest < 1,
+ * nfilter < 0, an id out of range in the test set or the filter. */
 kb2e_status kb2e_evaluate(kb2e_ctx* ctx, const int32_t* heads, const int32_t* tails, const int32_t* relations,
                           int64_t ntest, const int32_t* filter_heads, const int32_t* filter_tails,
                           const int32_t* filter_relations, int64_t nfilter, double* out);

@@ -1892,7 +1892,7 @@ EvalTables eval_tables(kb2e_ctx* c) {
 kb2e_status kb2e_evaluate(kb2e_ctx* c, const int32_t* th, const int32_t* tt, const int32_t* tr, int64_t ntest,
                           const int32_t* fh, const int32_t* ft, const int32_t* fr, int64_t nfilter, double* out) {
     return guarded(c, [&] {
-        if (!th || !tt || !tr || ntest < 1 || !out || (nfilter > 0 && (!fh || !ft || !fr)))
+        if (!th || !tt || !tr || ntest < 1 || !out || nfilter < 0 || (nfilter > 0 && (!fh || !ft || !fr)))
             return fail(c, KB2E_EINVAL, "empty test set");
         if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
         HIPCHK(hipSetDevice(c->cfg.device));
@@ -1906,7 +1906,7 @@ kb2e_status kb2e_evaluate_transr_compat(kb2e_ctx* c, const int32_t* th, const in
                                         int64_t nfilter, double* work, double* out,
                                         void (*progress)(double fraction, void* user), void* user) {
     return guarded(c, [&] {
-        if (!th || !tt || !tr || ntest < 1 || !out || (nfilter > 0 && (!fh || !ft || !fr)))
+        if (!th || !tt || !tr || ntest < 1 || !out || nfilter < 0 || (nfilter > 0 && (!fh || !ft || !fr)))
             return fail(c, KB2E_EINVAL, "empty test set");
         if (c->cfg.model != KB2E_TRANSR) return fail(c, KB2E_EUNSUPPORTED, "TransR only");
         if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");

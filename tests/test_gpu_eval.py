@@ -1,6 +1,8 @@
 """GPU link-prediction evaluator vs the reference's eval binaries (golden) and
 the oracle.  Energies are bit-identical FP64 restatements, so mean ranks and
-hits@10 must match exactly (no ties in these tables)."""
+hits@10 must match exactly.  The stateless cases here use tables without ties
+and compare the four means; the ranks one by one, ties with the truth, the
+candidate-block, query-tile and filter edges are test_gpu_eval_ranks.py's."""
 import os
 
 import numpy as np
