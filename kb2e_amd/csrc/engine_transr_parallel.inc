@@ -381,6 +381,14 @@ int32_t pipe_opt_bits() {
     return e && e[0] ? (int32_t)(atoi(e) & kPipeOptAll) : kPipeOptAll;
 }
 
+// the entity rows' y-row fetch and the gradient kernel's partial stores (a bit each: kRowsOptDeep,
+// kRowsOptStore; default all, KB2E_RPAR_ROWS_OPT=0 the path before them: A/B and the bit comparisons
+// of the tests; read at every batch)
+int32_t rows_opt_bits() {
+    const char* e = getenv("KB2E_RPAR_ROWS_OPT");
+    return e && e[0] ? (int32_t)(atoi(e) & kRowsOptAll) : kRowsOptAll;
+}
+
 // kPipeOptDefer: the chunks from which a relation defers its records (KB2E_RPAR_REC_DEFER; 0: none
 // does, 1: every relation with a pair, tests; the results do not depend on it; read at every batch)
 constexpr int32_t kRecDeferChunks = 12;  // (swept 4 / 8 / 12 / 16 on the bench: DESIGN.md 7, round 11)
@@ -448,6 +456,7 @@ void fill_rpar(kb2e_ctx* c, int64_t b, int j, int set, RParArgs& a, RParBufs<T>&
     bf.relpair = c->rpar_relpair.as<T>();
     bf.relpair_stamp = c->rpar_relpair_stamp.as<uint32_t>();
     bf.err = c->dataflow_err.as<uint32_t>() + 1;
+    bf.rows_opt = rows_opt_bits();
     if (c->rpar_mfma) {
         bf.pflag = buf_set(set, c->rpar_pflag, c->sb_pflag).as<uint8_t>();
         bf.cons_tile = buf_set(set, c->rpar_cons_tile, c->sb_cons_tile).as<int32_t>();

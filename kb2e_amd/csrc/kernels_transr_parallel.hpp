@@ -230,6 +230,9 @@ struct RParBufs {
     int32_t rec_cap;     // pipelined chain kernel: records a stage-full of its record pass (0: all that fit the LDS; tests)
     int32_t pipe_opt;    // pipelined chain kernel: the steps outside its violator loop (KB2E_RPAR_PIPE_OPT bits,
                          // kPipeOpt*; 0: the path before them.  The same bits on either path)
+    int32_t rows_opt;    // the entity rows' y-row fetch and the gradient kernel's partial stores
+                         // (KB2E_RPAR_ROWS_OPT bits, kRowsOpt*; 0: the path before them.  Loads and stores
+                         // only: the same bits on either path)
     int32_t* vio;        // n <= 64 chain kernels: [tiles][kCPairs] the violators' slots of the relation whose
                          // first tile it is (-2: (entity[r], r)); its pair records are made in-kernel
     uint32_t* err;       // pipelined chain: a bounded in-workgroup wait timed out (the host fails loudly)
@@ -246,6 +249,14 @@ struct RParBufs {
 // measured and dropped: DESIGN.md 7, round 10)
 constexpr int32_t kPipeOptHandover = 2, kPipeOptDefer = 8, kPipeOptPublish = 16;
 constexpr int32_t kPipeOptAll = kPipeOptHandover | kPipeOptDefer | kPipeOptPublish;
+
+// RParBufs::rows_opt, a bit a step: 2 the gradient pass of the entity rows fetches kEntDeep y rows at a time
+// (rpar_entity_events), 4 the gradient kernel skips the partials of a tile without an active update and
+// stores the others two columns a lane (transr_grad_wave_block).  (1, a relation's row groups spread over
+// workgroups, and 8, the relation blocks ahead of the entity blocks in the fused launch, were measured
+// and dropped: DESIGN.md 7, round 12)
+constexpr int32_t kRowsOptDeep = 2, kRowsOptStore = 4;
+constexpr int32_t kRowsOptAll = kRowsOptDeep | kRowsOptStore;
 
 __host__ __device__ constexpr int rm_up16_host_dev(int v) { return (v + 15) & ~15; }
 constexpr int kCPairs = 64;  // transRNorm pairs of a tile (4 St + 1 <= 64)
@@ -858,6 +869,7 @@ constexpr int kRParWaves = 16;
 // are, and the first addend of every step is the chain), and x + (+-0) = x for every x but -0; the columns past
 // n of the last step here are such terms too (W's element replaced by +0, G's lanes past n hold +0).
 constexpr int kRecSteps = 4;
+constexpr int kEntDeep = 16;  // kRowsOptDeep: y rows in flight (the pair rows of the record pass stay at four: round 12)
 template <typename T>
 __device__ __forceinline__ void rpar_record_convert(const RParArgs& a, const RParBufs<T>& bf, int r, T (&v)[2]) {
     typedef T T2 __attribute__((ext_vector_type(2)));
@@ -902,19 +914,59 @@ __device__ __forceinline__ int rpar_entity_last(const RParArgs& a, int p0, int p
     return last;
 }
 
+// The next D (at most) events of the mask m, in event order: their rows of `tab` fetched together -- D loads
+// in flight, one round trip -- the deferred ones converted (rpar_record_convert), then added in event order
+// to acc, or to acc2 for the events of pm.  The depth changes no sum: a row is added after the rows of the
+// events before it whatever the grouping.
+template <typename T, bool GRAD, int D>
+__device__ __forceinline__ void rpar_entity_group(const RParArgs& a, const RParBufs<T>& bf, const T* tab, int mine, int rdef,
+                                                  T c, uint64_t& m, uint64_t pm, bool defer, T (&acc)[2], T (&acc2)[2]) {
+    const int n = a.n, ld = a.ld;
+    int ev[D];
+    int k = 0;
+#pragma unroll
+    for (int q = 0; q < D; ++q)
+        if (m) {
+            ev[q] = __builtin_ctzll(m);
+            m &= m - 1;
+            k = q + 1;
+        }
+    T v[D][2];
+#pragma unroll
+    for (int q = 0; q < D; ++q)
+        if (q < k) lane_pair_load(tab + (int64_t)readlane_i32(mine, ev[q]) * ld, n, v[q]);
+    if (defer && __ballot(rdef >= 0)) {  // deferred records: G -> da, before they are added
+#pragma unroll
+        for (int q = 0; q < D; ++q)
+            if (q < k) {
+                const int rq = readlane_i32(rdef, ev[q]);
+                if (rq >= 0) rpar_record_convert<T>(a, bf, rq, v[q]);
+            }
+    }
+#pragma unroll
+    for (int q = 0; q < D; ++q)
+        if (q < k) {
+            const T cq = GRAD ? readlane_f(c, ev[q]) : T(1);
+            T(&dst)[2] = ((pm >> ev[q]) & 1) ? acc2 : acc;
+            dst[0] += cq * v[q][0];
+            dst[1] += cq * v[q][1];
+        }
+}
+
 // Events [p0 + 64 first, ...) of an entity segment in chunks of 64 (lane q:
 // event q); the rows the active ones add (y rows, or transRNorm pair deltas)
-// are then fetched four at a time, so a long segment keeps several loads in
-// flight instead of one dependent chain per event.  acc / dirty: the deltas
+// are then fetched four at a time (the y rows with kRowsOptDeep: kEntDeep at a time), so
+// a long segment keeps several loads in flight instead of one dependent chain per event.  acc / dirty: the deltas
 // (GRAD, and !GRAD without last_renorm: all of them; with it: the pre ones),
 // acc2 / dirty2: the post ones of update `last`.
 template <typename T, bool GRAD>
 __device__ __forceinline__ void rpar_entity_events(const RParArgs& a, const RParBufs<T>& bf, int row, int p0, int p1,
                                                    int first, int stride, int last, T (&acc)[2], T (&acc2)[2],
                                                    bool& dirty, bool& dirty2, bool& er_seen) {
-    const int n = a.n, ld = a.ld, l = lane_id();
+    const int l = lane_id();
     const bool split = !GRAD && bf.last_renorm;
     const bool defer = !GRAD && bf.rec_stamp != nullptr;  // (wave-uniform: only the pipelined chain defers records)
+    const bool deep = GRAD && (bf.rows_opt & kRowsOptDeep) != 0;
     for (int base = p0 + first * kWave; base < p1; base += stride * kWave) {
         const int p = base + l;
         int src = -1;     // row of the y / pair table this lane's event adds (GRAD: its y row)
@@ -962,33 +1014,10 @@ __device__ __forceinline__ void rpar_entity_events(const RParArgs& a, const RPar
             const int mine = pass ? src2 : src;
             uint64_t m = __ballot(mine >= 0);
             const uint64_t pm = __ballot(post);
-            while (m) {
-                int ev[4];
-                int k = 0;
-                for (; k < 4 && m; ++k) {
-                    ev[k] = __builtin_ctzll(m);
-                    m &= m - 1;
-                }
-                T v[4][2];
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (q < k) lane_pair_load(tab + (int64_t)readlane_i32(mine, ev[q]) * ld, n, v[q]);
-                if (defer && __ballot(rdef >= 0)) {  // deferred records: G -> da, before they are added
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (q < k) {
-                            const int rq = readlane_i32(rdef, ev[q]);
-                            if (rq >= 0) rpar_record_convert<T>(a, bf, rq, v[q]);
-                        }
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (q < k) {
-                        const T cq = GRAD ? readlane_f(c, ev[q]) : T(1);
-                        T(&dst)[2] = ((pm >> ev[q]) & 1) ? acc2 : acc;
-                        dst[0] += cq * v[q][0];
-                        dst[1] += cq * v[q][1];
-                    }
+            if (deep) {
+                while (m) rpar_entity_group<T, GRAD, kEntDeep>(a, bf, tab, mine, rdef, c, m, pm, defer, acc, acc2);
+            } else {
+                while (m) rpar_entity_group<T, GRAD, 4>(a, bf, tab, mine, rdef, c, m, pm, defer, acc, acc2);
             }
         }
     }
@@ -1083,11 +1112,34 @@ __device__ __forceinline__ void transr_entity_block(RParArgs a, RParBufs<T> bf, 
             acc[1] = part[0][1][l];
             acc2[0] = part[0][2][l];
             acc2[1] = part[0][3][l];
-            for (int v = 1; v < kRParWaves; ++v) {
-                acc[0] += part[v][0][l];
-                acc[1] += part[v][1][l];
-                acc2[0] += part[v][2][l];
-                acc2[1] += part[v][3][l];
+            // waves 1 .. 15 in order.  The gradient pass reads five waves' partials at a time: all
+            // fifteen at once are 60 values live under the 128 registers of a 1024-thread block,
+            // and they spilled there (acc2, the post deltas, is the record pass's alone: zero and unread here).
+            // The same sums in the same order, so no bit of rows_opt gates it.  The record pass keeps all
+            // its reads together: it compiles without scratch
+            if constexpr (GRAD) {
+                static_assert((kRParWaves - 1) % 5 == 0, "the combine reads five waves at a time");
+#pragma unroll 1
+                for (int v0 = 1; v0 < kRParWaves; v0 += 5) {
+                    T pv[5][2];
+#pragma unroll
+                    for (int v = 0; v < 5; ++v) {
+                        pv[v][0] = part[v0 + v][0][l];
+                        pv[v][1] = part[v0 + v][1][l];
+                    }
+#pragma unroll
+                    for (int v = 0; v < 5; ++v) {
+                        acc[0] += pv[v][0];
+                        acc[1] += pv[v][1];
+                    }
+                }
+            } else {
+                for (int v = 1; v < kRParWaves; ++v) {
+                    acc[0] += part[v][0][l];
+                    acc[1] += part[v][1][l];
+                    acc2[0] += part[v][2][l];
+                    acc2[1] += part[v][3][l];
+                }
             }
             rpar_entity_finish<T, GRAD>(a, bf, row, acc, acc2, flags[0] != 0, flags[2] != 0, flags[1] != 0, last);
         }

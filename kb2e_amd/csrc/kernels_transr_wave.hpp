@@ -204,18 +204,27 @@ __device__ __forceinline__ void transr_grad_wave_block(const RParArgs& a, const 
     // export row and coefficient
     int rowu[kSteps];
     T cu[kSteps];
+    bool any_act = false;
 #pragma unroll
     for (int s = 0; s < kSteps; ++s) {
         const int u = 4 * s + kq;
         const int kk = a.td_kk[t * 8 + (u >> 1)], side = u & 1;
+        const bool au = u < nu && a.act[kk];
         rowu[s] = kk * 2 + side;
-        cu[s] = (u < nu && a.act[kk]) ? (T)(-(side ? 1.0 : -1.0) * a.lr) : T(0);
+        cu[s] = au ? (T)(-(side ? 1.0 : -1.0) * a.lr) : T(0);
+        any_act |= au;
     }
+    // kRowsOptStore: a tile without an active update has tile_act 0 below, and the partials' only
+    // reader on this path (the gradient pass of transr_rel_rows_wave / transr_rel_rows4_wave) skips it
+    // by that flag: its all-zero partials are neither computed nor stored.  The tile's wpart / rpart
+    // slots then keep whatever an earlier batch left there: a reader must go by tile_act
+    const bool o_store = (bf.rows_opt & kRowsOptStore) != 0;
+    const bool skip = o_store && __ballot(any_act) == 0;
     T* const wp = bf.wpart + (int64_t)bid * n * ld;
 #pragma unroll
     for (int q = 0; q < kOut; ++q) {
         const int tile = w + kConsWaves * q;
-        if (tile >= NB * NB) break;
+        if (tile >= NB * NB || skip) break;
         const int jb = tile / NB, ib = tile % NB;
         const int j = jb * 16 + l16, i = ib * 16 + l16;
         T av[kSteps], bv[kSteps];
@@ -227,10 +236,30 @@ __device__ __forceinline__ void transr_grad_wave_block(const RParArgs& a, const 
         typename M::acc_t acc = {T(0), T(0), T(0), T(0)};
 #pragma unroll
         for (int s = 0; s < kSteps; ++s) acc = M::mma(av[s], bv[s], acc);
+        if (o_store) {
+            // the same values, 16 bytes (two columns of a row) a store: lanes 2 c and 2 c + 1 hold columns
+            // i and i + 1 of the same four rows; the even lane takes both columns of its rows 0 and 2, the
+            // odd lane those of rows 1 and 3 (moves only; an odd n leaves the last column on its own)
+            typedef T T2 __attribute__((ext_vector_type(2)));
+            const bool odd = l & 1;
+            const T g0 = dpp_mov<0xB1>(odd ? acc[0] : acc[1]);  // quad_perm [1, 0, 3, 2]: the neighbour's
+            const T g1 = dpp_mov<0xB1>(odd ? acc[2] : acc[3]);
+            const int ic = i & ~1;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int jj = jb * 16 + M::row(l, k);
-            if (jj < n && i < n) wp[(int64_t)jj * ld + i] = acc[k];
+            for (int h = 0; h < 2; ++h) {
+                const int k = 2 * h + (odd ? 1 : 0);
+                const int jj = jb * 16 + M::row(l, k);
+                const T mine = acc[k], theirs = h ? g1 : g0;
+                T* const dst = wp + (int64_t)jj * ld + ic;
+                if (jj < n && ic + 1 < n) *(T2*)dst = odd ? T2{theirs, mine} : T2{mine, theirs};
+                else if (jj < n && ic < n) *dst = odd ? theirs : mine;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int jj = jb * 16 + M::row(l, k);
+                if (jj < n && i < n) wp[(int64_t)jj * ld + i] = acc[k];
+            }
         }
         if (jb == 0) {  // dr over this column block: row 0 of (c^T) X, c in row 0 of A
             typename M::acc_t dr = {T(0), T(0), T(0), T(0)};
