@@ -175,7 +175,8 @@ kb2e_status kb2e_set_sample_stream(kb2e_ctx* ctx, const int32_t* i, const int32_
                                    const uint8_t* side, int64_t count);
 
 /* The sample stream of the epoch in progress (after its first batch was
- * queued): up to `count` samples in order.  Returns KB2E_ESTATE between epochs. */
+ * queued) or, between epochs, of the last one: up to `count` samples in order.
+ * Returns KB2E_ESTATE before the first epoch on the uploaded triple set. */
 kb2e_status kb2e_get_sample_stream(kb2e_ctx* ctx, int32_t* i, int32_t* j, uint8_t* side, int64_t count);
 
 /* One epoch of Trainer::bfgs (common/trainer.cpp:72-106): numBatches batches of

@@ -145,6 +145,7 @@ struct kb2e_ctx {
     // at the epoch boundary (swap_index) -- no index build on the batches' stream
     int64_t prefetch_gen = 0, committed_gen = -1, index_pre_gen = -2;
     bool next_pending = false;  // launch_next after the epoch's first batch
+    bool stream_drawn = false;  // set cur holds an epoch's stream of the current triple set
     hipEvent_t ev_index = nullptr;
     hipEvent_t ev_sampled = nullptr, ev_epoch_done = nullptr;
     bool host_sampler = false;     // KB2E_HOST_SAMPLER=1: draw on the host (debug)
@@ -598,18 +599,7 @@ void ensure_jump_table(kb2e_ctx* c) {
     // M (the window after kGlibcBlock words from the window before) and its squares
     constexpr int D = GlibcRand::kDeg;
     std::vector<uint32_t> P((size_t)kGlibcPowLevels * D * D);
-    for (int j = 0; j < D; ++j)
-        for (int m = 0; m < D; ++m) P[(size_t)j * D + m] = C[(size_t)m * kGlibcBlock + (kGlibcBlock - D + j)];
-    for (int k = 1; k < kGlibcPowLevels; ++k) {
-        const uint32_t* A = P.data() + (size_t)(k - 1) * D * D;
-        uint32_t* Q = P.data() + (size_t)k * D * D;
-        for (int i = 0; i < D; ++i)
-            for (int j = 0; j < D; ++j) {
-                uint32_t v = 0;
-                for (int m = 0; m < D; ++m) v += A[i * D + m] * A[m * D + j];
-                Q[i * D + j] = v;
-            }
-    }
+    glibc_pow_table(kGlibcBlock, kGlibcPowLevels, C.data(), P.data());
     c->glibc_pow.alloc(P.size() * 4);
     HIPCHK(hipMemcpy(c->glibc_pow.p, P.data(), P.size() * 4, hipMemcpyHostToDevice));
 }
@@ -622,6 +612,9 @@ void launch_prefetch(kb2e_ctx* c) {
     const int set = c->cur ^ 1;
     const int64_t nraw = (int64_t)(c->words_per_sample * c->S) + 4096;
     const bool doubling = c->sampler_doubling || getenv("KB2E_SAMPLER_DOUBLING");
+    // next[] holds word positions up to nraw in 32 bits: a buffer grown past that by the
+    // x1.5 retries (start_epoch_stream) would wrap them
+    if (nraw >= INT32_MAX) throw std::runtime_error("sampler word buffer too large");
     ensure_sampler_capacity(c, nraw, doubling);
     c->nraw = nraw;
     ensure_jump_table(c);
@@ -1086,6 +1079,7 @@ void run_batches(kb2e_ctx* c, int64_t count) {
                 if (counts) HIPCHK(hipStreamSynchronize(c->stream));
             }
             c->epoch_ready = true;
+            c->stream_drawn = true;
             c->reduced_upto = 0;
         }
         c->prof_batch = (c->prof_counter++ % c->prof_period) == 0;
@@ -1474,6 +1468,7 @@ kb2e_status kb2e_upload_triples(kb2e_ctx* c, const int32_t* h, const int32_t* t,
         c->have_triples = true;
         c->epoch_pos = 0;
         c->epoch_ready = false;
+        c->stream_drawn = false;
         return KB2E_OK;
     });
 }
@@ -1725,7 +1720,8 @@ kb2e_status kb2e_set_sample_stream(kb2e_ctx* c, const int32_t* i, const int32_t*
 
 kb2e_status kb2e_get_sample_stream(kb2e_ctx* c, int32_t* i, int32_t* j, uint8_t* side, int64_t count) {
     return guarded(c, [&] {
-        if (!c->epoch_ready) return fail(c, KB2E_ESTATE, "no epoch in progress");
+        // (between epochs set cur still holds the last one's: the prefetch writes the other set)
+        if (!c->stream_drawn) return fail(c, KB2E_ESTATE, "no epoch started on this triple set");
         const int64_t k = std::min<int64_t>(count, c->S);
         HIPCHK(hipStreamSynchronize(c->stream));
         HIPCHK(hipMemcpy(i, c->si(), k * 4, hipMemcpyDeviceToHost));

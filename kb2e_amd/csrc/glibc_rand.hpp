@@ -108,6 +108,26 @@ inline void glibc_jump_table(int L, uint32_t* C) {
         for (int m = 0; m < D; ++m) C[(size_t)m * L + t] = at(t - GlibcRand::kSep, m) + at(t - D, m);
 }
 
+// The L-word jump as a matrix and its squares: P[k] = M^(2^k), row-major 31 x 31,
+// k < levels, where M takes the window before a block of L words to the window
+// after it (rows L-31..L-1 of the jump table C = glibc_jump_table(L, .)).  The
+// device multiplies the squares of a block number's set bits (kernels_glibc.hpp).
+inline void glibc_pow_table(int L, int levels, const uint32_t* C, uint32_t* P) {
+    constexpr int D = GlibcRand::kDeg;
+    for (int j = 0; j < D; ++j)
+        for (int m = 0; m < D; ++m) P[(size_t)j * D + m] = C[(size_t)m * L + (L - D + j)];
+    for (int k = 1; k < levels; ++k) {
+        const uint32_t* A = P + (size_t)(k - 1) * D * D;
+        uint32_t* Q = P + (size_t)k * D * D;
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j < D; ++j) {
+                uint32_t v = 0;
+                for (int m = 0; m < D; ++m) v += A[i * D + m] * A[m * D + j];
+                Q[i * D + j] = v;
+            }
+    }
+}
+
 // common/utils.cpp:113-120 -- (rand() * rand()) % x in int32 with wrap-around
 // (the product overflows in practice; both factors are consumed either way).
 inline int32_t rand_max(GlibcRand& g, int32_t x) {
