@@ -781,10 +781,12 @@ int64_t kb2e_device_bytes(const kb2e_ctx* ctx);
  *     T <- renorm(T0 + sum_r (T_r - T0))
  * where T0 is the tables after the previous merge: the entity deltas are
  * reduce-scattered to the owner of each block of rows over RCCL, the owner
- * adds them and re-applies the model's norm constraint to the rows any rank
- * changed (as kb2e_renormalize), and an all-gather returns the merged table;
- * relation and weight deltas are all-reduced and every rank renormalises the
- * changed rows.  All work runs on the contexts' own streams; the calls return
+ * adds them and re-applies the model's norm constraint (as kb2e_renormalize) to
+ * the changed units -- a unit (a row; for the TransR weights one relation's
+ * whole matrix) is renormalised when its SUMMED delta has a non-zero element,
+ * and a row whose deltas cancel exactly across the ranks is left as it was --
+ * and an all-gather returns the merged table; relation and weight deltas are
+ * all-reduced and every rank renormalises the changed units.  All work runs on the contexts' own streams; the calls return
  * when the merged tables are in place.  Two ways to build the communicator:
  *  - one process per GPU (torchrun): rank 0 makes an id with
  *    kb2e_comm_unique_id, the caller hands it to every rank (any side channel),

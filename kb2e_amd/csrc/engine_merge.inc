@@ -13,9 +13,10 @@
 //   2. RCCL: a reduce-scatter of the entity deltas to the owner of each block
 //      of rows, an all-reduce (sum) of the relation and weight deltas (one
 //      ncclGroup);
-//   3. each owner adds the summed deltas to its block and renormalises the rows
-//      any rank changed (the model's constraint, renorm_rows); every rank does
-//      the same for the relations and weights (identical sums everywhere);
+//   3. each owner adds the summed deltas to its block and renormalises the units
+//      whose summed delta has a non-zero element (the model's constraint,
+//      renorm_rows; a row whose deltas cancel exactly is left as it was); every
+//      rank does the same for the relations and weights (identical sums everywhere);
 //   4. RCCL: an all-gather of the owners' blocks;
 //   5. the merged tables become the next epoch's base.
 // The collectives come either from RCCL -- one communicator per rank

@@ -9,8 +9,9 @@ table deltas and re-apply the reference's norm constraints:
 
 * relations and the relation weights (TransH normals, TransR matrices): one
   all-reduce (sum) of the deltas over RCCL, then every rank renormalises the
-  rows any rank changed (the same rows on every rank: the summed delta is the
-  same everywhere);
+  units whose summed delta has a non-zero element (a row whose deltas cancel
+  exactly is left as it was; the same rows on every rank: the summed delta is
+  the same everywhere);
 * entities: a reduce-scatter of the deltas to the owner of each contiguous
   block of rows, the owner adds them, renormalises its changed rows, and an
   all-gather hands every rank the merged table -- the all-reduce's bytes, but

@@ -146,7 +146,7 @@ def test_merge_needs_a_communicator():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("model", ["E", "R"])
+@pytest.mark.parametrize("model", ["E", "H", "R"])
 def test_cli_two_gpus_matches_python_group(tmp_path, model):
     """bin/trainTrans* --gpus 2 (one process driving two contexts) prints the
     epoch losses of the Python group driver on the same shards and seeds."""
@@ -154,7 +154,7 @@ def test_cli_two_gpus_matches_python_group(tmp_path, model):
     d = str(tmp_path)
     data.write(ds, d)
     dim, epochs, seed = 20, 3, 11
-    exe = os.path.join(ROOT, "bin", {"E": "trainTransE", "R": "trainTransR"}[model])
+    exe = os.path.join(ROOT, "bin", {"E": "trainTransE", "H": "trainTransH", "R": "trainTransR"}[model])
     cmd = [exe, "--datadir", d, "--outdir", d, "--size", str(dim), "--epochs", str(epochs), "--batches", "20",
            "--seed", str(seed), "--rate", "0.01", "--schedule", "1", "--gpus", "2"]
     if model == "R":  # TransE seed files from a one-GPU TransE run
