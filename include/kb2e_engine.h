@@ -550,6 +550,54 @@ kb2e_status kb2e_complete_triples(kb2e_ctx* ctx, const int32_t* relations, int64
                                   int32_t exclude_loops, int32_t* heads /* [nrel][k] */, int32_t* tails /* [nrel][k] */,
                                   double* energy /* [nrel][k] */, int64_t* found /* [nrel] */);
 
+/* ---- Entity neighbours: which entities lie close to a given one?  Over all
+ * entities as queries this is the k-nearest-neighbour graph of the model, and
+ * two entities that list each other are the candidates for being the same
+ * thing -- the counterpart of the conjunctive queries above, which match a
+ * record to a known entity.  The call follows the contract of "Using a trained
+ * model" above: read-only (tables, training state, glibc stream and TransR work
+ * vectors stay), stateless FP64 arithmetic with transr_compat ignored, FP32
+ * tables widened first, every model, distance, precision and dim, every device
+ * buffer freed before return (also on the error paths), one stream
+ * synchronisation, at the end.
+ *   Space.  relation == -1: the entity space, P(x) is row x of the entity
+ *   table.  relation == r >= 0: relation r's space, P(x) is the evaluator's
+ *   projection for r -- TransE the row itself, TransH x - (w_r . x) w_r, TransR
+ *   M_r x from zeroed work vectors -- which answers "similar as an argument
+ *   of r".
+ *   Distance.  d(a, x) = sum_k |P(x)_k - P(a)_k| (L1) or sum_k (P(x)_k -
+ *   P(a)_k)^2 (L2), the norm of the context's energies (a TransH context is
+ *   L1), one serial FP64 sum over k from zero in the evaluator's operand order:
+ *   bit for bit the energy kb2e_score_triples gives (a, x, r) when relation
+ *   r's vector is zero, and in the entity space that of a TransE model on the
+ *   same entity table with a zero relation.  d(a, x) and d(x, a) have the same
+ *   bits.
+ *   Output.  Per query the found[q] = min(k, candidates) nearest entities in
+ *   ascending (distance, entity id) order in ids[q*k + j], dist[q*k + j]; slots
+ *   at and after found[q] hold -1 and +inf.  The candidates are all |E|
+ *   entities, minus entities[q] itself when include_self == 0.  An entity may
+ *   be queried more than once; each listing is answered.
+ *   Limits.  1 <= k <= 128 (k may exceed |E|).  The bound is a choice of the
+ *   fused kernel's LDS budget -- 16 query rows, each with a k-list and a
+ *   staging list of 12-byte records, 48 KiB at k = 128 -- not of the method.
+ * Nothing of size nq x |E| is ever allocated.  Besides the projected table
+ * [dim][|E|] and the outputs, the call's device memory is the partial records
+ * (rows of a chunk x candidate slices x k, 12 bytes each), and nq is walked in
+ * chunks so that they stay under 64 MiB whatever nq and |E| are
+ * (KB2E_NEIGHBORS_CHUNK_ROWS=<rows> lowers the chunk, for tests).  The
+ * candidates are cut into slices so that tiles x slices fills the card
+ * (KB2E_NEIGHBORS_SLICE=<candidates> forces the slice length, tests; it is
+ * raised where one tile's partial records would not fit the cap).  Selection
+ * is on the total order (distance bits, entity id) of distinct values: the
+ * result does not depend on the launch geometry, the slice length, the
+ * chunking or the order in which candidates were appended.
+ * KB2E_EINVAL: nq < 1, k out of range, include_self other than 0 / 1, relation
+ * outside -1..|R|-1, an entity id out of range, a NULL array with a
+ * count > 0. */
+kb2e_status kb2e_neighbors(kb2e_ctx* ctx, const int32_t* entities, int64_t nq, int32_t relation, int32_t k,
+                           int32_t include_self, int32_t* ids /* [nq][k] */, double* dist /* [nq][k] */,
+                           int32_t* found /* [nq] */);
+
 /* ---- Entity fold-in: give new entities a row without retraining.  The free
  * entities' rows of the device entity table are learnt from example triples
  * while everything else is frozen: every other entity row, the relation and
@@ -740,7 +788,8 @@ int32_t kb2e_rng_next(kb2e_ctx* ctx);
  * "classify_sort" (every radix pass), "classify_fit" (segment starts and both
  * sweeps); kb2e_corrupt_triples: "classify_corrupt"; kb2e_complete_triples:
  * "complete_score" (projection + the tile kernel), "complete_select";
- * kb2e_fold_in_entities: "foldin"; kb2e_fold_in_relations: "foldrel").  Returns total
+ * kb2e_neighbors: "neighbors_score" (projection + the fused score and select
+ * kernel), "neighbors_merge"; kb2e_fold_in_entities: "foldin"; kb2e_fold_in_relations: "foldrel").  Returns total
  * milliseconds and launch count since kb2e_profile_enable.  on = 0: off;
  * on = P >= 1: the batch kernels of every P-th batch are timed (event records
  * cost device time of their own; sampling keeps the rest of the run unperturbed),
@@ -757,6 +806,11 @@ kb2e_status kb2e_profile_query(kb2e_ctx* ctx, const char* name, double* total_ms
  * "complete_candidates" -- pairs scored, "complete_records" -- records
  * appended, "complete_strips" -- score + select steps,
  * "complete_buffer_records" -- the record buffer's capacity in records.
+ * Of the last kb2e_neighbors call: "neighbors_candidates" -- pairs scored,
+ * "neighbors_slices" -- (tile, candidate slice) workgroups of the fused kernel,
+ * "neighbors_chunks" -- runs of queries that shared the partial records,
+ * "neighbors_prunes" -- cuts of a row's list to its k best, each of which
+ * lowered that row's bound.
  * Of the last kb2e_predict_joint / kb2e_rank_joint call (kept on the host):
  * "joint_chunks" -- runs of queries that shared the key buffer, "joint_rows" --
  * constraint rows scored, "joint_projections" -- per-relation projections made.

@@ -31,6 +31,7 @@
 #include "predict.hpp"
 #include "classify.hpp"
 #include "complete.hpp"
+#include "neighbors.hpp"
 #include "foldin.hpp"
 #include "foldrel.hpp"
 #include "host_data.hpp"
@@ -179,6 +180,7 @@ struct kb2e_ctx {
     uint32_t hpar_stamp = 0;
     DevBuf hpar_clk;                       // KB2E_HPAR_CLK: the w-apply workgroups' clocks (diagnostic)
     CompleteStats complete_stats;  // kb2e_complete_triples: the last call's counters (kb2e_counter)
+    NeighborsStats neighbors_stats;  // kb2e_neighbors: likewise
     JointStats joint_stats;        // kb2e_predict_joint / kb2e_rank_joint: likewise
     PathStats path_stats;          // kb2e_predict_path / kb2e_rank_path: likewise
     DevBuf hpar_count;                     // PARALLEL TransH: normOrth iterations of the last two batches, relation passes run
@@ -2133,6 +2135,21 @@ kb2e_status kb2e_complete_triples(kb2e_ctx* c, const int32_t* relations, int64_t
     });
 }
 
+kb2e_status kb2e_neighbors(kb2e_ctx* c, const int32_t* entities, int64_t nq, int32_t relation, int32_t k,
+                           int32_t include_self, int32_t* ids, double* dist, int32_t* found) {
+    return guarded(c, [&] {
+        if (!entities || nq < 1 || !ids || !dist || !found)
+            return fail(c, KB2E_EINVAL, "no entities to find neighbours of");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        c->neighbors_stats = NeighborsStats{};
+        neighbors(eval_tables(c), NeighborsQuery{entities, nq, relation, k, include_self}, ids, dist, found,
+                  &c->neighbors_stats, &hooks);
+        return KB2E_OK;
+    });
+}
+
 kb2e_status kb2e_fold_in_entities(kb2e_ctx* c, const int32_t* free_entities, int64_t nfree, const int32_t* heads,
                                   const int32_t* tails, const int32_t* relations, int64_t count, const int32_t* kh,
                                   const int32_t* kt, const int32_t* kr, int64_t nknown, int32_t epochs, uint64_t seed,
@@ -2214,6 +2231,13 @@ kb2e_status kb2e_counter(kb2e_ctx* c, const char* name, int64_t* value) {
             if (nm == "complete_records") return *value = cs.records, KB2E_OK;
             if (nm == "complete_strips") return *value = cs.strips, KB2E_OK;
             if (nm == "complete_buffer_records") return *value = cs.buffer_records, KB2E_OK;
+        }
+        if (value && nm.rfind("neighbors_", 0) == 0) {  // kb2e_neighbors: the last call
+            const NeighborsStats& ns = c->neighbors_stats;
+            if (nm == "neighbors_candidates") return *value = ns.candidates, KB2E_OK;
+            if (nm == "neighbors_slices") return *value = ns.slices, KB2E_OK;
+            if (nm == "neighbors_chunks") return *value = ns.chunks, KB2E_OK;
+            if (nm == "neighbors_prunes") return *value = ns.prunes, KB2E_OK;
         }
         if (value && nm.rfind("joint_", 0) == 0) {  // kb2e_predict_joint / kb2e_rank_joint: the last call
             const JointStats& js = c->joint_stats;

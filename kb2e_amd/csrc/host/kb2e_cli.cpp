@@ -12,7 +12,9 @@
 // parameters for new relations with everything else frozen) and jointTransE /
 // jointTransH / jointTransR (conjunctive queries: the top-k entities that fit
 // several patterns at once) and pathTransE / pathTransH / pathTransR (path
-// queries: the top-k entities at the end of a relation path).
+// queries: the top-k entities at the end of a relation path) and
+// neighborsTransE / neighborsTransH / neighborsTransR (entity neighbours: the
+// k nearest entities of given entities or of all, and the mutual pairs).
 //
 // Same flags, defaults, stdout lines and files as the reference binaries
 // (transe/bin/trainTransE.cpp, common/args.cpp, common/loader.cpp,
@@ -43,6 +45,7 @@
 
 #include "../../../include/kb2e_engine.h"
 #include "../classify_host.hpp"
+#include "../neighbors_host.hpp"
 
 namespace kb2e_host {
 
@@ -141,6 +144,7 @@ void printUsage(const char* invoked) {  // common/args.cpp:125-142
     printf("   --topk [10] --constrained [1] (completeTrans*: heads / tails from the entities seen in that slot of the relation)\n");
     printf("   --loops [0] (completeTrans*: 1 = head == tail may be an answer)\n");
     printf("   --filtered [1] (completeTrans*: known = train + valid + test; 0 = train + valid)\n");
+    printf("   --entities FILE | --all, --topk [10] --relation NAME --self --pairs (neighborsTrans*: entity names, one per line, or every entity; the space of a relation instead of the entity space; the entity itself is a candidate; the mutual pairs instead of the lists)\n");
     printf("   --new FILE --foldout DIR (foldinTrans*: triples that mention the new entities; where the full entity table goes)\n");
     printf("   --epochs [1000] --seed [now] --side [2] (foldinTrans*: passes, seed of the new rows and of the negatives, slot to corrupt)\n");
     printf("   --new FILE --foldout DIR --epochs --seed --side --batch [1] (foldrelTrans*: the new relations' triples; where the full relation tables go; samples per batch)\n");
@@ -1046,6 +1050,82 @@ int complete_main(int argc, char** argv, kb2e_model model) {
     return 0;
 }
 
+// neighborsTransE|H|R: entity neighbours (kb2e_neighbors) on the tables
+// evalTrans* loads.  --entities FILE names the query entities, one per line
+// (unknown names are reported and skipped, in the loader's wording), --all asks
+// for every entity: the kNN graph.  --topk K [10], --relation NAME: relation
+// NAME's projected space instead of the entity space, --self: the entity itself
+// is a candidate.  One line per answer: entity name, position (from 1),
+// neighbour name, distance.  --pairs: the mutual pairs of the lists instead, one
+// line each: the two names and the distance, ascending.
+int neighbors_main(int argc, char** argv, kb2e_model model) {
+    EmbeddingArguments args = parseArgs(argc, argv);
+    printf("%s\n", args.to_string().c_str());
+    int i, topk = 10, relation = -1;
+    std::string entFile, relName;
+    if ((i = argpos("entities", true, argc, argv)) != -1) entFile = argv[i + 1];
+    if ((i = argpos("topk", true, argc, argv)) != -1) topk = atoi(argv[i + 1]);
+    if ((i = argpos("relation", true, argc, argv)) != -1) relName = argv[i + 1];
+    const bool all = argpos("all", false, argc, argv) != -1;
+    const int self = argpos("self", false, argc, argv) != -1 ? 1 : 0;
+    const bool pairs = argpos("pairs", false, argc, argv) != -1;
+    if (all == !entFile.empty()) {
+        printf("Give either --entities FILE or --all\n");
+        exit(1);
+    }
+    FILE* f = nullptr;
+    if (!all && !(f = fopen(entFile.c_str(), "r"))) {
+        printf("Could not open entity file: %s\n", entFile.c_str());
+        exit(2);
+    }
+    LoadedModel L;
+    load_model(args, model, L);
+    std::vector<std::string> names(L.entity2id.size());
+    for (const auto& kv : L.entity2id)
+        if (kv.second >= 0 && (size_t)kv.second < names.size()) names[(size_t)kv.second] = kv.first;
+    if (!relName.empty()) {
+        if (!L.relation2id.count(relName)) {
+            std::cout << "Relation found in triple file that was not found in the identity file: " << relName << std::endl;
+            exit(1);
+        }
+        relation = L.relation2id[relName];
+    }
+    std::vector<int32_t> ents;
+    if (f) {
+        char eb[512];
+        while (fscanf(f, "%511s", eb) == 1) {
+            if (!L.entity2id.count(eb)) {
+                std::cout << "Entity found in triple file that was not found in the identity file: " << eb << std::endl;
+                continue;
+            }
+            ents.push_back(L.entity2id[eb]);
+        }
+        fclose(f);
+    } else {
+        for (size_t e = 0; e < names.size(); ++e) ents.push_back((int32_t)e);
+    }
+    if (ents.empty()) {
+        printf("No entities to find neighbours of\n");
+        exit(1);
+    }
+    const size_t nq = ents.size(), k = (size_t)std::max(topk, 1);
+    std::vector<int32_t> ids(nq * k), found(nq);
+    std::vector<double> dist(nq * k);
+    check(L.ctx, kb2e_neighbors(L.ctx, ents.data(), (int64_t)nq, relation, topk, self, ids.data(), dist.data(), found.data()),
+          "neighbors");
+    if (pairs) {
+        for (const kb2e::MutualPair& p : kb2e::mutual_pairs(ents.data(), (int64_t)nq, (int32_t)k, ids.data(), dist.data(), found.data()))
+            printf("%s\t%s\t%.6lf\n", names[(size_t)p.a].c_str(), names[(size_t)p.b].c_str(), p.dist);
+    } else {
+        for (size_t q = 0; q < nq; ++q)
+            for (int32_t j = 0; j < found[q]; ++j)
+                printf("%s\t%d\t%s\t%.6lf\n", names[(size_t)ents[q]].c_str(), j + 1, names[(size_t)ids[q * k + j]].c_str(),
+                       dist[q * k + j]);
+    }
+    kb2e_destroy(L.ctx);
+    return 0;
+}
+
 // foldinTransE|H|R: rows for entities the model was not trained on
 // (kb2e_fold_in_entities).  --datadir D holds entity2id.txt with the old
 // entities first and the new ones after them; the tables in --outdir O have rows
@@ -1363,9 +1443,12 @@ int main(int argc, char** argv) {
     if (prog == "pathTransE") return path_main(argc, argv, KB2E_TRANSE);
     if (prog == "pathTransH") return path_main(argc, argv, KB2E_TRANSH);
     if (prog == "pathTransR") return path_main(argc, argv, KB2E_TRANSR);
+    if (prog == "neighborsTransE") return neighbors_main(argc, argv, KB2E_TRANSE);
+    if (prog == "neighborsTransH") return neighbors_main(argc, argv, KB2E_TRANSH);
+    if (prog == "neighborsTransR") return neighbors_main(argc, argv, KB2E_TRANSR);
     fprintf(stderr,
             "invoke as trainTransE|H|R, evalTransE|H|R, predictTransE|H|R, classifyTransE|H|R, completeTransE|H|R, "
-            "foldinTransE|H|R, foldrelTransE|H|R, jointTransE|H|R or pathTransE|H|R (got %s)\n",
+            "foldinTransE|H|R, foldrelTransE|H|R, jointTransE|H|R, pathTransE|H|R or neighborsTransE|H|R (got %s)\n",
             prog.c_str());
     return 2;
 }

@@ -32,6 +32,7 @@ EXPORTS = [
     "kb2e_rank_triples", "kb2e_predict_relations", "kb2e_rank_relations", "kb2e_fit_thresholds",
     "kb2e_classify_triples", "kb2e_corrupt_triples", "kb2e_complete_triples", "kb2e_fold_in_entities",
     "kb2e_fold_in_relations", "kb2e_predict_joint", "kb2e_rank_joint", "kb2e_predict_path", "kb2e_rank_path",
+    "kb2e_neighbors",
 ]
 COMM_ID_BYTES = 128
 PATH_MAX_HOPS = 8  # KB2E_PATH_MAX_HOPS
@@ -112,6 +113,7 @@ def lib():
                                            i32p, i32p, C.POINTER(i64)]),
             "kb2e_complete_triples": (i32, [vp, i32p, i64, i32, i32p, i32p, i32p, i64, i32, i32, i32p, i32p, dp,
                                             C.POINTER(i64)]),
+            "kb2e_neighbors": (i32, [vp, i32p, i64, i32, i32, i32, i32p, dp, i32p]),
             "kb2e_fold_in_entities": (i32, [vp, i32p, i64, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, i32, C.c_uint64,
                                             i32, i32, dp, dp, dp, C.POINTER(i64)]),
             "kb2e_fold_in_relations": (i32, [vp, i32p, i64, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, i32, i64,
@@ -645,6 +647,31 @@ class Engine:
                                                 int(constrained), int(exclude_loops), _ip(heads), _ip(tails), _dp(en),
                                                 found.ctypes.data_as(C.POINTER(C.c_int64))), "complete_triples")
         return heads, tails, en, found
+
+    # ------------------------------------------------ entity neighbours
+    def neighbors(self, entities, k, relation=-1, include_self=False):
+        """The k nearest entities of each listed entity, in the entity space
+        (relation -1: the rows of the entity table) or in relation r's space (the
+        evaluator's projection for r).  The distance is the context's norm of
+        P(x) - P(a), L1 or squared L2, in score()'s bits for (a, x, r) with a zero
+        relation vector; the entity itself is a candidate only with include_self.
+        1 <= k <= 128.  Returns (ids int32[nq, k], dist float64[nq, k], found
+        int32[nq]): ascending (distance, id), padded with -1 / +inf after found[q]."""
+        e = np.ascontiguousarray(entities, dtype=np.int32).reshape(-1)
+        nq, k = len(e), int(k)
+        if include_self not in (0, 1, False, True):
+            raise EngineError("neighbors: EINVAL: include_self must be 0 or 1")
+        kk = max(k, 1)
+        ids = np.full((nq, kk), -1, np.int32)
+        dist = np.full((nq, kk), np.inf)
+        found = np.zeros(nq, np.int32)
+        self._check(lib().kb2e_neighbors(self.h, _ip(e), nq, int(relation), k, int(include_self), _ip(ids), _dp(dist),
+                                         _ip(found)), "neighbors")
+        return ids, dist, found
+
+    def knn_graph(self, k, relation=-1):
+        """neighbors() of every entity, itself left out: row a lists a's k nearest."""
+        return self.neighbors(np.arange(self.ne, dtype=np.int32), k, relation=relation)
 
     # ------------------------------------------------ entity fold-in
     def fold_in(self, free, examples, known=None, *, epochs, seed=0, side=2, max_sweeps=0, rows=None):

@@ -34,6 +34,10 @@ test triples that mention an entity, with the entity taken out, are one
 conjunctive query (``Engine.rank_joint``) that should rank it first.
 ``path_evaluation`` ranks the tail of every test triple at the end of a relation
 path that reaches its head through train triples (``Engine.rank_path``).
+``duplicate_detection`` is the hold-out measure of entity neighbours
+(``Engine.knn_graph``): twins are planted (``duplicate_split``), the model is
+trained on the split set, and each twin's original is looked up among the
+twin's nearest entities and among the graph's mutual pairs (``mutual_pairs``).
 """
 from __future__ import annotations
 
@@ -548,4 +552,129 @@ def path_evaluation(eng, ds, hops=(1, 2, 3), beam=64, seed=0, limit=None):
             raise ValueError("no test triple has a path of %d hops" % m)
         ranks = np.asarray(eng.rank_path(anchors, paths, truth, filt, beam=beam)).reshape(-1, 2)
         out[m] = {"count": int(len(anchors)), "raw": rank_metrics(ranks[:, 0]), "filtered": rank_metrics(ranks[:, 1])}
+    return out
+
+
+def mutual_pairs(ids, dist, found, entities=None):
+    """The duplicate candidates of a kNN graph.  `ids`, `dist`, `found` are
+    ``Engine.neighbors`` output; row q is the list of entities[q] (None: of
+    entity q, as ``Engine.knn_graph`` returns it; an entity listed twice counts
+    once, its first listing).  A pair (a, b), a < b, is mutual when b is among
+    a's found neighbours and a among b's.  Returns (pairs int32[m, 2], dist
+    float64[m]): the distance is the one listed in a's row, the order ascending
+    (distance, a, b)."""
+    ids = np.asarray(ids, dtype=np.int64)
+    dist = np.asarray(dist, dtype=np.float64)
+    found = np.asarray(found, dtype=np.int64).reshape(-1)
+    nq, k = ids.shape
+    ents = np.arange(nq, dtype=np.int64) if entities is None else np.asarray(entities, dtype=np.int64).reshape(-1)
+    if len(ents) != nq:
+        raise ValueError("entities and ids differ in length")
+    if nq:
+        _, first = np.unique(ents, return_index=True)
+        keep = np.zeros(nq, bool)
+        keep[first] = True
+    else:
+        keep = np.zeros(0, bool)
+    live = (np.arange(k)[None, :] < found[:, None]) & keep[:, None]
+    a = np.broadcast_to(ents[:, None], ids.shape)[live]
+    b = ids[live]
+    d = dist[live]
+    span = int(max(ents.max(initial=0), ids.max(initial=0))) + 1
+    edge = a * span + b
+    back = b * span + a
+    sel = (a < b) & np.isin(back, edge)
+    a, b, d = a[sel], b[sel], d[sel]
+    order = np.lexsort((b, a, d))
+    return np.stack([a[order], b[order]], axis=1).astype(np.int32).reshape(-1, 2), d[order]
+
+
+def duplicate_split(ds, count, seed=0):
+    """Plant duplicates: `count` entities with at least 4 training triples are
+    drawn (``numpy.random.default_rng(seed)``), each gets a twin with the id
+    |E| + i (i its position among the drawn entities, ascending by id), and each
+    training triple that mentions the entity is moved to the twin -- the entity
+    replaced by the twin wherever the triple names it -- on a fair coin of the
+    same stream; where the coins leave fewer than two triples on a side, the
+    first triples of the other side, in file order, change over.  Valid and test
+    stay.  Returns (Dataset with |E| + count entities and as many training
+    triples as before, pairs int32[count, 2] of (original, twin))."""
+    train = np.array(ds.train, dtype=np.int32).reshape(-1, 3)
+    ne = int(ds.num_entities)
+    mentions = np.bincount(np.concatenate([train[:, 0], train[train[:, 1] != train[:, 0], 1]]), minlength=ne)
+    eligible = np.flatnonzero(mentions >= 4)
+    if count < 0 or count > len(eligible):
+        raise ValueError(f"{count} twins asked for, {len(eligible)} entities have at least 4 training triples")
+    rng = np.random.default_rng(seed)
+    chosen = np.sort(rng.choice(eligible, size=count, replace=False))
+    pairs = np.stack([chosen, ne + np.arange(count)], axis=1).astype(np.int32).reshape(-1, 2)
+    # (the mentions are read from the caller's triples: a twin never gets a twin of its own)
+    src = np.asarray(ds.train, dtype=np.int32).reshape(-1, 3)
+    for e, twin in pairs.tolist():
+        rows = np.flatnonzero((src[:, 0] == e) | (src[:, 1] == e))
+        move = rng.integers(0, 2, size=len(rows)).astype(bool)
+        for side in (True, False):  # at least two moved, at least two kept
+            short = 2 - int((move == side).sum())
+            if short > 0:
+                move[np.flatnonzero(move != side)[:short]] = side
+        for i in rows[move].tolist():
+            for slot in (0, 1):
+                if src[i, slot] == e:
+                    train[i, slot] = twin
+    out = data.Dataset(ne + count, ds.num_relations, train, np.asarray(ds.valid), np.asarray(ds.test))
+    return out, pairs
+
+
+def duplicate_metrics(ids, dist, found, pairs, k):
+    """``duplicate_detection``'s numbers from a kNN graph (``Engine.knn_graph``
+    output, row = entity) and the planted (original, twin) pairs: recall@1 and
+    recall@k of "the twin's original is among the twin's nearest", the mutual
+    pairs of the graph, the planted pairs among them and their share, and the
+    random baseline k / (|E| - 1)."""
+    ids = np.asarray(ids)
+    found = np.asarray(found).reshape(-1)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    ne = len(ids)
+    hit1 = hitk = 0
+    for orig, twin in pairs.tolist():
+        row = ids[twin, :found[twin]]
+        hit1 += int(len(row) > 0 and row[0] == orig)
+        hitk += int(orig in row[:k].tolist())
+    mp, md = mutual_pairs(ids, dist, found)
+    planted = {(min(a, b), max(a, b)) for a, b in pairs.tolist()}
+    got = [p for p in map(tuple, mp.tolist()) if p in planted]
+    n = len(pairs)
+    return {"k": int(k), "entities": int(ne), "planted": int(n),
+            "recall@1": hit1 / n if n else None, "recall@k": hitk / n if n else None,
+            "mutual": int(len(mp)), "mutual_planted": got,
+            "mutual_share": len(got) / len(mp) if len(mp) else None,
+            "baseline": k / (ne - 1) if ne > 1 else None}
+
+
+def duplicate_detection(ds, model, dim, count, *, epochs, k=10, seed=0, relation=-1, rate=0.001, margin=1.0,
+                        method=1, distance=0, batches=100, train_seed=7, schedule="ordered", device=0,
+                        make_engine=Engine):
+    """Which two known entities are the same thing?  The hold-out measure of
+    ``Engine.knn_graph``: `count` duplicates are planted (``duplicate_split``
+    with `seed`), the model is trained `epochs` epochs on the split set, the
+    k-nearest-neighbour graph of all entities is built on the device in the
+    entity space (or relation `relation`'s), and the planted pairs are looked up
+    in it (``duplicate_metrics``).  Returns its dict with "pairs" added."""
+    split, pairs = duplicate_split(ds, count, seed)
+    eng = make_engine(model, dim, split.num_entities, split.num_relations, rate=rate, margin=margin, method=method,
+                      distance=distance, batches=batches, seed=train_seed, transr_compat=False, device=device,
+                      schedule=schedule)
+    try:
+        eng.upload_triples(split.train)
+        ent, rel, _ = eng.init_params()
+        if model in ("R", "transr", 2):
+            eng.transr_seed(ent, rel)
+        for _ in range(epochs):
+            eng.train_epoch()
+        eng.synchronize()
+        ids, dist, found = eng.knn_graph(k, relation=relation)
+    finally:
+        eng.close()
+    out = duplicate_metrics(ids, dist, found, pairs, k)
+    out["pairs"] = pairs
     return out
