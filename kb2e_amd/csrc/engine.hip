@@ -79,6 +79,7 @@ void build_owner_index(kb2e_ctx* c);
 void prepare_relowner_kernels();
 void setup_transr_parallel(kb2e_ctx* c);
 void build_transr_tiles(kb2e_ctx* c, bool tiles, hipStream_t st, int set);
+void rpar_index_stats(const kb2e_ctx* c);
 template <typename T>
 void run_batch_transr_parallel(kb2e_ctx* c, int64_t b);
 template <typename T, int CH>
@@ -1080,6 +1081,7 @@ void run_batches(kb2e_ctx* c, int64_t count) {
                 build_index(c, c->stream, c->cur);
                 if (counts) HIPCHK(hipStreamSynchronize(c->stream));
             }
+            if (counts && getenv("KB2E_RPAR_INDEX_STATS")) rpar_index_stats(c);  // (tools)
             c->epoch_ready = true;
             c->stream_drawn = true;
             c->reduced_upto = 0;

@@ -47,8 +47,12 @@ size_t rmfma_lds(const kb2e_ctx* c, bool cons) {
 }
 
 // run_l [kScanChunk][2n] + the chunk-prefix partials [1024 / 2n][2n] (1024-thread blocks)
-size_t rpar_scan_lds(const kb2e_ctx* c) {
-    return (size_t)kScanChunk * 2 * c->n * 8 + (size_t)std::max(1, 1024 / (2 * c->n)) * 2 * c->n * 8;
+// (ahead, the kPassOptScan kernels, n <= 64: a set of partials for every sub-batch a block reads ahead -- a
+// thread takes at most two of the kScanQuarters (set, run) slots a sub-batch: rpar_scan_ahead_slots)
+size_t rpar_scan_lds(const kb2e_ctx* c, bool ahead = false) {
+    const int G = std::max(1, 1024 / (2 * c->n));
+    const int sets = ahead && c->n <= 64 ? std::max(1, std::min<int>(c->sub, 2 * G / kScanQuarters)) : 1;
+    return (size_t)kScanChunk * 2 * c->n * 8 + (size_t)sets * G * 2 * c->n * 8;
 }
 
 // Matrix-core path: the largest St <= 8 whose tile and transRNorm images both
@@ -152,12 +156,13 @@ void setup_transr_parallel(kb2e_ctx* c) {
     c->rpar_rel_begin.alloc((size_t)c->nbi * 4);
     c->rpar_brel_cap = std::min<int64_t>(g.num_relations, c->Bs);
     c->rpar_brel.alloc((size_t)c->nbi * c->rpar_brel_cap * 4);
-    c->rpar_bnrel.alloc((size_t)c->nbi * 4);
+    // (three counts an index batch: its relations, its entity segments, the long ones of them: rel_list_kernel)
+    c->rpar_bnrel.alloc((size_t)c->nbi * 3 * 4);
     for (int32_t** h : {&c->pin_bnrel, &c->pin_sh_bnrel}) {
         if (*h) (void)hipHostFree(*h);
         *h = nullptr;
-        HIPCHK(hipHostMalloc((void**)h, (size_t)c->nbi * 4, 0));
-        std::memset(*h, 0, (size_t)c->nbi * 4);
+        HIPCHK(hipHostMalloc((void**)h, (size_t)c->nbi * 3 * 4, 0));
+        std::memset(*h, 0, (size_t)c->nbi * 3 * 4);
     }
     if (c->rpar_widep) c->rpar_wsc.alloc((size_t)c->rpar_brel_cap * c->n * c->ld * 8);
     else c->rpar_wsc.free();
@@ -300,8 +305,12 @@ void setup_transr_parallel(kb2e_ctx* c) {
     }
     for (const void* k : {(const void*)rpar_scan_energy_kernel<double>, (const void*)rpar_scan_energy_kernel<float>,
                           (const void*)rpar_scan_energy_merged_kernel<double>,
-                          (const void*)rpar_scan_energy_merged_kernel<float>})
-        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rpar_scan_lds(c));
+                          (const void*)rpar_scan_energy_merged_kernel<float>,
+                          (const void*)rpar_scan_energy_ahead_kernel<double>,
+                          (const void*)rpar_scan_energy_ahead_kernel<float>,
+                          (const void*)rpar_scan_energy_merged_ahead_kernel<double>,
+                          (const void*)rpar_scan_energy_merged_ahead_kernel<float>})
+        (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rpar_scan_lds(c, true));
     // a refused limit above (an image no launch of this context uses) must not linger
     // as the sticky last error for the next launch check
     (void)hipGetLastError();
@@ -328,9 +337,10 @@ void build_transr_tiles(kb2e_ctx* c, bool tiles, hipStream_t st, int set) {
                                                      c->seg_row.as<int32_t>(), c->cfg.num_entities,
                                                      c->rel_order.as<int32_t>(), c->cfg.num_relations,
                                                      c->rpar_brel_cap, c->rpar_brel.as<int32_t>(),
-                                                     c->rpar_bnrel.as<int32_t>());
+                                                     c->rpar_bnrel.as<int32_t>(), c->seg_start.as<int32_t>(),
+                                                     kRParLongMin);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(c->pin_bnrel, c->rpar_bnrel.p, (size_t)c->nbi * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(c->pin_bnrel, c->rpar_bnrel.p, (size_t)c->nbi * 3 * 4, hipMemcpyDeviceToHost, st));
     }
     if (c->rpar_td_r.p) {  // the wave kernels' tile descriptors
         RTileDescArgs d{};
@@ -387,6 +397,37 @@ int32_t pipe_opt_bits() {
 int32_t rows_opt_bits() {
     const char* e = getenv("KB2E_RPAR_ROWS_OPT");
     return e && e[0] ? (int32_t)(atoi(e) & kRowsOptAll) : kRowsOptAll;
+}
+
+// the entity passes' wave-a-segment form and the compat energy launch's loads ahead of its barriers (a bit
+// each: kPassOptRound, kPassOptScan; default all, KB2E_RPAR_PASS_OPT=0 the path before them: A/B and the bit
+// comparisons of the tests; read at every batch)
+int32_t pass_opt_bits() {
+    const char* e = getenv("KB2E_RPAR_PASS_OPT");
+    return e && e[0] ? (int32_t)(atoi(e) & kPassOptAll) : kPassOptAll;
+}
+
+// KB2E_RPAR_INDEX_STATS (tools): the epoch's index batches in figures, one line to stderr an epoch -- mean,
+// minimum and maximum over the index batches of the entity segments, of those with kRParLongMin events or
+// more, of the relations, and of the relation-row waves with a relation (four rows a wave for n <= 64)
+void rpar_index_stats(const kb2e_ctx* c) {
+    const int64_t nb = c->nbi;
+    const int rw = c->n <= 64 ? (c->n + 4) / 4 : c->n + 1;
+    const char* names[4] = {"entity segments", "segments >= 128 events", "relations", "relation-row waves"};
+    fprintf(stderr, "rpar index: %lld index batches", (long long)nb);
+    for (int k = 0; k < 4; ++k) {
+        const int32_t* p = c->pin_bnrel + (k == 0 ? nb : k == 1 ? 2 * nb : 0);
+        int64_t sum = 0, lo = INT64_MAX, hi = 0;
+        for (int64_t b = 0; b < nb; ++b) {
+            const int64_t v = (int64_t)p[b] * (k == 3 ? rw : 1);
+            sum += v;
+            lo = std::min(lo, v);
+            hi = std::max(hi, v);
+        }
+        fprintf(stderr, "; %s mean %.1f min %lld max %lld", names[k], nb ? (double)sum / nb : 0.0, (long long)lo,
+                (long long)hi);
+    }
+    fprintf(stderr, "\n");
 }
 
 // kPipeOptDefer: the chunks from which a relation defers its records (KB2E_RPAR_REC_DEFER; 0: none
@@ -457,6 +498,7 @@ void fill_rpar(kb2e_ctx* c, int64_t b, int j, int set, RParArgs& a, RParBufs<T>&
     bf.relpair_stamp = c->rpar_relpair_stamp.as<uint32_t>();
     bf.err = c->dataflow_err.as<uint32_t>() + 1;
     bf.rows_opt = rows_opt_bits();
+    bf.pass_opt = pass_opt_bits();
     if (c->rpar_mfma) {
         bf.pflag = buf_set(set, c->rpar_pflag, c->sb_pflag).as<uint8_t>();
         bf.cons_tile = buf_set(set, c->rpar_cons_tile, c->sb_cons_tile).as<int32_t>();
@@ -600,9 +642,14 @@ void run_subbatch_transr_parallel(kb2e_ctx* c, int64_t b, int j) {
                 rpar_scan_prefix_kernel<<<(2 * c->n + 31) / 32, 1024, 0, sa>>>(
                     c->rpar_scan.as<double>(), nchunks, 2 * c->n, c->transr_work.as<double>(), pre);
             }
-            rpar_scan_energy_kernel<T><<<nchunks, 1024, rpar_scan_lds(c), sa>>>(
-                a, bfa, c->rpar_scan.as<double>(), nchunks, c->transr_work.as<double>(),
-                c->transr_work_alt.as<double>(), pre);
+            if (rpar_scan_ahead_slots(bfa.pass_opt, c->n, 0) == 1)  // kPassOptScan, n <= 64
+                rpar_scan_energy_ahead_kernel<T><<<nchunks, 1024, rpar_scan_lds(c, true), sa>>>(
+                    a, bfa, c->rpar_scan.as<double>(), nchunks, c->transr_work.as<double>(),
+                    c->transr_work_alt.as<double>(), pre);
+            else
+                rpar_scan_energy_kernel<T><<<nchunks, 1024, rpar_scan_lds(c), sa>>>(
+                    a, bfa, c->rpar_scan.as<double>(), nchunks, c->transr_work.as<double>(),
+                    c->transr_work_alt.as<double>(), pre);
             HIPCHK(hipGetLastError());
             std::swap(c->transr_work.p, c->transr_work_alt.p);  // the carried work vectors, ping-pong
             if (c->rpar_cons_wave) grad_wave_launch<T>(a, bfa, tgrid, sa);
@@ -656,17 +703,44 @@ void transr_phase_b(kb2e_ctx* c, RParArgs a, RParBufs<T> bf) {
                                                                      : transr_rows_kernel<T, P, 0>;
     };
     using yes1 = std::true_type;
+    // kPassOptRound: 256-thread workgroups, a wave a short entity segment, a workgroup for every four entity
+    // segments of the index batch (their count came to the host with the index, behind the relation counts);
+    // the fused launches' relation-row workgroups follow, four waves each
+    // -- while the segments are a few rounds of the GPU's waves at the most: with many more, workgroups that
+    // stride over the segments win (K5, ~144,000 segments an index batch: 17.5 ms a batch against 18.3 in this
+    // form; ~5,100 and ~8,000, the FB15k shape at k = 2 and 1, gain; between them nobody has measured:
+    // DESIGN.md 7, round 13)
+    constexpr int kRoundSegMax = 4 * 256 * kRParWaves;  // four times the waves of the grid before
+    const int nseg_ent = c->pin_bnrel[c->nbi + a.batch];
+    if (nseg_ent < 0 || nseg_ent > (int64_t)c->B * c->slots)
+        throw std::logic_error("batch entity segment count out of range");
+    const bool round1 = (bf.pass_opt & kPassOptRound) != 0 && nseg_ent <= kRoundSegMax;
+    const int egrid4 = std::max(1, (nseg_ent + kEntWaves - 1) / kEntWaves);
+    const int fgrid4 = egrid4 + (rw + 3) / 4;
+    auto rows4_fn = [&](auto pass1) {
+        constexpr bool P = decltype(pass1)::value;
+        return rmode == 4 ? transr_rows4_kernel<T, P, 4> : rmode == 8 ? transr_rows4_kernel<T, P, 8>
+                                                                     : transr_rows4_kernel<T, P, 0>;
+    };
+    auto entity_launch = [&](auto grad, hipEvent_t ev1) {  // the entity rows alone
+        constexpr bool G = decltype(grad)::value;
+        if (round1) c->launch(transr_entity4_kernel<T, G>, dim3(egrid4), dim3(256), 0, nullptr, ev1, a, bf, kRParLongMin);
+        else c->launch(transr_entity_kernel<T, G>, dim3(egrid), dim3(1024), 0, nullptr, ev1, a, bf, kRParLongMin);
+    };
+    auto rows_launch = [&](auto pass1, hipEvent_t ev0, hipEvent_t ev1) {  // the fused launch of a pass
+        if (round1) c->launch(rows4_fn(pass1), dim3(fgrid4), dim3(256), 0, ev0, ev1, a, bf, kRParLongMin, egrid4);
+        else c->launch(rows_fn(pass1), dim3(fgrid), dim3(1024), 0, ev0, ev1, a, bf, kRParLongMin, egrid);
+    };
     if (c->rpar_no_constraint) {
         c->ev_end(e1);
-        c->launch(rows_fn(yes1()), dim3(fgrid), dim3(1024), 0, e0, e1, a, bf, kRParLongMin, egrid);
+        rows_launch(yes1(), e0, e1);
         return;
     }
     if (fuse) {
-        c->launch(rows_fn(yes1()), dim3(fgrid), dim3(1024), 0, e0, nullptr, a, bf, kRParLongMin, egrid);
+        rows_launch(yes1(), e0, nullptr);
     } else {
         c->launch(transr_rel_rows_kernel<T, true>, dim3(rgrid), dim3(256), 0, e0, nullptr, a, bf);
-        transr_entity_kernel<T, true><<<egrid, 1024, 0, c->stream>>>(a, bf, kRParLongMin);
-        HIPCHK(hipGetLastError());
+        entity_launch(yes1(), nullptr);
     }
     if (mf && c->rpar_cons_seq) {
         if constexpr (std::is_same<T, double>::value) cons_seq_launch(a, bf, c->rpar_seq_lds, c->stream);
@@ -686,15 +760,15 @@ void transr_phase_b(kb2e_ctx* c, RParArgs a, RParBufs<T> bf) {
     c->ev_end(e1);
     const char* f2 = getenv("KB2E_RPAR_FUSE2");
     if (c->rpar_cons_seq || c->rpar_cons_wide || c->rpar_cons_gen) {  // the matrices are final: only the entity rows take pair records
-        c->launch(transr_entity_kernel<T, false>, dim3(egrid), dim3(1024), 0, nullptr, e1, a, bf, kRParLongMin);
+        entity_launch(std::false_type(), e1);
     } else if (f2 && f2[0] == '1') {
-        c->launch(rows_fn(std::false_type()), dim3(fgrid), dim3(1024), 0, nullptr, e1, a, bf, kRParLongMin, egrid);
+        rows_launch(std::false_type(), nullptr, e1);
     } else {
         if (rmode == 4) transr_rel_rows4_kernel<T, false, 4><<<(rel_waves4 + 3) / 4, 256, 0, c->stream>>>(a, bf);
         else if (rmode == 8) transr_rel_rows4_kernel<T, false, 8><<<(rel_waves4 + 3) / 4, 256, 0, c->stream>>>(a, bf);
         else transr_rel_rows_kernel<T, false><<<rgrid, 256, 0, c->stream>>>(a, bf);
         HIPCHK(hipGetLastError());
-        c->launch(transr_entity_kernel<T, false>, dim3(egrid), dim3(1024), 0, nullptr, e1, a, bf, kRParLongMin);
+        entity_launch(std::false_type(), e1);
     }
 }
 
@@ -723,8 +797,15 @@ void run_batch_transr_merged(kb2e_ctx* c, int64_t b) {
             const int grid = (m.sub - 1) * m.nch + last;
             rpar_scan_sums_merged_kernel<<<grid, 256, 0, c->stream>>>(a0.proj, m, c->ld, c->n,
                                                                          c->rpar_scan.as<double>());
-            rpar_scan_energy_merged_kernel<T><<<grid, 1024, rpar_scan_lds(c), c->stream>>>(
-                a0, bf0, m, c->rpar_scan.as<double>(), c->transr_work.as<double>(), c->transr_work_alt.as<double>());
+            // kPassOptScan: when the last sub-batch's blocks can take their slots (at most two a thread)
+            if (rpar_scan_ahead_slots(bf0.pass_opt, c->n, m.sub - 1))
+                rpar_scan_energy_merged_ahead_kernel<T><<<grid, 1024, rpar_scan_lds(c, true), c->stream>>>(
+                    a0, bf0, m, c->rpar_scan.as<double>(), c->transr_work.as<double>(),
+                    c->transr_work_alt.as<double>());
+            else
+                rpar_scan_energy_merged_kernel<T><<<grid, 1024, rpar_scan_lds(c), c->stream>>>(
+                    a0, bf0, m, c->rpar_scan.as<double>(), c->transr_work.as<double>(),
+                    c->transr_work_alt.as<double>());
             HIPCHK(hipGetLastError());
             std::swap(c->transr_work.p, c->transr_work_alt.p);  // the carried work vectors: one ping-pong a batch
         }

@@ -83,13 +83,29 @@ struct RParArgs {
 // Per batch b (a block each): the relations with a segment in the batch (segments
 // [rel_begin[b], batch_seg[b + 1]), sorted by row), listed in training-frequency order
 // (rel_order) -- the chain kernels' blocks, so that a launch covers exactly the
-// batch's relations, hot ones first -- and their count.
+// batch's relations, hot ones first -- and their count.  Behind the nb counts, in nrel too: every batch's
+// entity segments (nrel[nb + b]: the grid of the entity passes in their wave-a-segment form, kPassOptRound)
+// and how many of them have long_min events or more (nrel[2 nb + b]: statistics).
 static __attribute__((unused)) __global__ __launch_bounds__(1024) void rel_list_kernel(
     const int32_t* rel_begin, const int32_t* batch_seg, const int32_t* seg_row, int32_t ne, const int32_t* rel_order,
-    int32_t nr, int64_t cap, int32_t* brel, int32_t* nrel) {
+    int32_t nr, int64_t cap, int32_t* brel, int32_t* nrel, const int32_t* seg_start, int32_t long_min) {
     __shared__ int32_t wsum[16];
+    __shared__ int32_t nlong;
     const int b = blockIdx.x, t = threadIdx.x, w = t >> 6, l = t & 63;
     const int s0 = rel_begin[b], s1 = batch_seg[b + 1];
+    {
+        const int nb = gridDim.x, e0 = batch_seg[b];
+        if (t == 0) nlong = 0;
+        __syncthreads();
+        int nl = 0;
+        for (int s = e0 + t; s < s0; s += blockDim.x) nl += seg_start[s + 1] - seg_start[s] >= long_min;
+        if (nl) atomicAdd(&nlong, nl);
+        __syncthreads();
+        if (t == 0) {
+            nrel[nb + b] = s0 - e0;
+            nrel[2 * nb + b] = nlong;
+        }
+    }
     int32_t* out = brel + (int64_t)b * cap;
     int total = 0;
     for (int base = 0; base < nr; base += 1024) {
@@ -233,7 +249,10 @@ struct RParBufs {
     int32_t rows_opt;    // the entity rows' y-row fetch and the gradient kernel's partial stores
                          // (KB2E_RPAR_ROWS_OPT bits, kRowsOpt*; 0: the path before them.  Loads and stores
                          // only: the same bits on either path)
-    int32_t* vio;        // n <= 64 chain kernels: [tiles][kCPairs] the violators' slots of the relation whose
+    int32_t pass_opt;    // the entity passes' wave-a-segment form and the compat energy launch's loads ahead of
+                         // its barriers (KB2E_RPAR_PASS_OPT bits, kPassOpt*; 0: the path before them.  Which wave
+                         // takes which segment and when a load is issued only: the same bits on either path)
+    int32_t* vio;       // n <= 64 chain kernels: [tiles][kCPairs] the violators' slots of the relation whose
                          // first tile it is (-2: (entity[r], r)); its pair records are made in-kernel
     uint32_t* err;       // pipelined chain: a bounded in-workgroup wait timed out (the host fails loudly)
     uint32_t* rec_stamp; // [R] batch stamp when the relation's pair records (bf.pair, bf.relpair) are still the
@@ -257,6 +276,14 @@ constexpr int32_t kPipeOptAll = kPipeOptHandover | kPipeOptDefer | kPipeOptPubli
 // and dropped: DESIGN.md 7, round 12)
 constexpr int32_t kRowsOptDeep = 2, kRowsOptStore = 4;
 constexpr int32_t kRowsOptAll = kRowsOptDeep | kRowsOptStore;
+
+// RParBufs::pass_opt, a bit a step: 1 the entity passes run as four-wave workgroups, a wave a short segment
+// and as many workgroups as the index batch has segments (transr_entity_block4), 4 the compat energy launch
+// issues every load that depends on no sum ahead of its first barrier (rpar_scan_energy_ahead).  (2, the head
+// loads of a wave's next segment ahead of the current one's finish, was not built: with bit 1 no wave takes
+// a second segment.  DESIGN.md 7, round 13)
+constexpr int32_t kPassOptRound = 1, kPassOptScan = 4;
+constexpr int32_t kPassOptAll = kPassOptRound | kPassOptScan;
 
 __host__ __device__ constexpr int rm_up16_host_dev(int v) { return (v + 15) & ~15; }
 constexpr int kCPairs = 64;  // transRNorm pairs of a tile (4 St + 1 <= 64)
@@ -1164,6 +1191,106 @@ __global__ __launch_bounds__(1024) void transr_entity_kernel(RParArgs a, RParBuf
     transr_entity_block<T, GRAD>(a, bf, long_min, blockIdx.x, gridDim.x);
 }
 
+// kPassOptRound: the entity rows of the four segments s0 + 4 bid .. + 3 (256 threads), a wave a short
+// segment, so no wave takes a second one and the hardware refills a CU as workgroups leave it (the launch has
+// a workgroup for every four entity segments of the index batch: rel_list_kernel's count).  A long segment
+// among the four takes the whole workgroup once its short ones are done: the sixteen chunk streams of
+// transr_entity_block (chunks st, st + 16, ...), four a wave (st = w, w + 4, ...) with accumulators of their
+// own, combined in stream order 0 .. 15 -- the same sums in the same order.
+constexpr int kEntWaves = 4;
+template <typename T, bool GRAD>
+__device__ __forceinline__ void transr_entity_block4(RParArgs a, RParBufs<T> bf, int32_t long_min, int bid) {
+    constexpr int NP = GRAD ? 2 : 4;  // (acc2, the post deltas, is the record pass's alone)
+    __shared__ T part[kRParWaves][NP][kWave];
+    __shared__ int flags[4];
+    const int w = threadIdx.x >> 6, l = lane_id();
+    const bool split = !GRAD && bf.last_renorm;
+    const int s1 = a.rel_begin[a.batch];  // entity segments sort first
+    const int sb = a.batch_seg[a.batch] + bid * kEntWaves;
+    if (sb >= s1) return;
+    // the four segments' bounds in one load (lane q: the start of segment sb + q), known to every wave
+    const int stl = (l <= kEntWaves && sb + l <= s1) ? a.seg_start[sb + l] : 0;
+    int lng = 0, p0 = 0, p1 = 0;
+#pragma unroll
+    for (int q = 0; q < kEntWaves; ++q) {
+        const int q0 = __shfl(stl, q), q1 = __shfl(stl, q + 1);
+        if (sb + q < s1 && q1 - q0 >= long_min) lng |= 1 << q;
+        if (q == w) p0 = q0, p1 = q1;
+    }
+    if (sb + w < s1 && !((lng >> w) & 1)) {  // short segment: this wave's
+        const int row = a.seg_row[sb + w];
+        const int last = split ? rpar_entity_last(a, p0, p1, 0, 1) : -1;
+        T acc[2] = {T(0), T(0)}, acc2[2] = {T(0), T(0)};
+        bool dirty = false, dirty2 = false, er = false;
+        rpar_entity_events<T, GRAD>(a, bf, row, p0, p1, 0, 1, last, acc, acc2, dirty, dirty2, er);
+        rpar_entity_finish<T, GRAD>(a, bf, row, acc, acc2, dirty, dirty2, er, last);
+    }
+    if (!lng) return;  // (the same in every wave of the workgroup)
+    for (int q = 0; q < kEntWaves; ++q) {
+        if (!((lng >> q) & 1)) continue;
+        p0 = __shfl(stl, q);
+        p1 = __shfl(stl, q + 1);
+        const int row = a.seg_row[sb + q];
+        if (threadIdx.x < 4) flags[threadIdx.x] = threadIdx.x == 3 ? -1 : 0;
+        __syncthreads();
+        int last = -1;
+        if (split) {  // the row's last update over the whole segment
+            last = rpar_entity_last(a, p0, p1, w, kEntWaves);
+            if (l == 0) atomicMax(&flags[3], last);
+            __syncthreads();
+            last = flags[3];
+        }
+        bool dirty = false, dirty2 = false, er = false;
+        for (int st = w; st < kRParWaves; st += kEntWaves) {  // chunks st, st + 16, ...
+            T acc[2] = {T(0), T(0)}, acc2[2] = {T(0), T(0)};
+            rpar_entity_events<T, GRAD>(a, bf, row, p0, p1, st, kRParWaves, last, acc, acc2, dirty, dirty2, er);
+            part[st][0][l] = acc[0];
+            part[st][1][l] = acc[1];
+            if constexpr (!GRAD) {
+                part[st][2][l] = acc2[0];
+                part[st][3][l] = acc2[1];
+            }
+        }
+        if (l == 0 && dirty) atomicOr(&flags[0], 1);
+        if (l == 0 && er) atomicOr(&flags[1], 1);
+        if (l == 0 && dirty2) atomicOr(&flags[2], 1);
+        __syncthreads();
+        if (w == 0) {
+            T acc[2] = {part[0][0][l], part[0][1][l]}, acc2[2] = {T(0), T(0)};
+            if constexpr (!GRAD) {
+                acc2[0] = part[0][2][l];
+                acc2[1] = part[0][3][l];
+            }
+            for (int v = 1; v < kRParWaves; ++v) {  // streams 1 .. 15 in order
+                acc[0] += part[v][0][l];
+                acc[1] += part[v][1][l];
+                if constexpr (!GRAD) {
+                    acc2[0] += part[v][2][l];
+                    acc2[1] += part[v][3][l];
+                }
+            }
+            rpar_entity_finish<T, GRAD>(a, bf, row, acc, acc2, flags[0] != 0, flags[2] != 0, flags[1] != 0, last);
+        }
+        __syncthreads();
+    }
+}
+
+template <typename T, bool GRAD>
+__global__ __launch_bounds__(256) void transr_entity4_kernel(RParArgs a, RParBufs<T> bf, int32_t long_min) {
+    transr_entity_block4<T, GRAD>(a, bf, long_min, blockIdx.x);
+}
+
+// transr_rows_kernel (below) with kPassOptRound: 256-thread workgroups throughout, the entity ones first
+template <typename T, bool PASS1, int RM>
+__global__ __launch_bounds__(256) void transr_rows4_kernel(RParArgs a, RParBufs<T> bf, int32_t long_min,
+                                                           int32_t egrid) {
+    const int gw = (((int)blockIdx.x - egrid) * (int)blockDim.x + (int)threadIdx.x) >> 6;
+    if ((int)blockIdx.x < egrid) transr_entity_block4<T, PASS1>(a, bf, long_min, blockIdx.x);
+    else if (RM == 4) transr_rel_rows4_wave<T, PASS1, 4>(a, bf, gw);
+    else if (RM == 8) transr_rel_rows4_wave<T, PASS1, 8>(a, bf, gw);
+    else transr_rel_rows_wave<T, PASS1>(a, bf, gw);
+}
+
 // Both row passes of one step in one launch (they touch disjoint tables):
 // workgroups [0, egrid) the entity rows, the rest one wave per (relation, row).
 // RM: the relation-row layout -- 0 a row a wave, 4 / 8 four rows a wave with 4 / 8
@@ -1381,6 +1508,162 @@ __device__ __forceinline__ void rpar_scan_energy_block(const RParArgs& a, const 
         ptab_insert(a, prel, pent, (int)(c0 / 2) * 4 + (int)threadIdx.x);
 }
 
+// kPassOptScan: the same chunk, every load whose address depends on no sum issued ahead of the first barrier.
+// A "set" is what one step of the chain of additions reads from memory: the grouped sums of the chunks before
+// a chunk (rpar_scan_parts' loads, summed as there: a thread's part is a function of `sums` alone) and the
+// chunk's calls.  Sub-batch j's block needs j + 1 sets: the last chunk of every sub-batch before it (the
+// carry-in of rpar_scan_carry_chain) and its own.  A set's calls are cut into kScanQuarters runs of sixteen,
+// and the G thread groups of 2 n threads (rpar_scan_parts' groups) take the (set, run) slots g, g + G, ...:
+// a thread fetches the sixteen calls of its slot for its element at the top, all slots at once, NS slots a
+// thread.  The chain of additions then walks the slots in order, a barrier a slot: the slot's threads take the
+// running values from `hand` (LDS; a set's first run starts as rpar_scan_start does, from the work vectors or
+// the set before and the parts), add their calls one after another as rpar_scan_calls does, and leave them
+// there.  The samples' relation rows are fetched at the top as well, by the wave that takes the sample.
+constexpr int kScanQuarters = kScanChunk / 16;
+constexpr int kScanWaveSamples = 2;  // samples a wave: kScanChunk / 2 over the 16 waves
+// the slots a thread of sub-batch j's block takes at 1024 threads a block (0: more than two -- the host then
+// launches the kernels of the path before)
+__host__ __device__ __forceinline__ int rpar_scan_ahead_slots(int32_t pass_opt, int n, int j) {
+    if (!(pass_opt & kPassOptScan) || n > 64) return 0;
+    const int G = 1024 / (2 * n), slots = kScanQuarters * (j + 1);
+    return slots <= G ? 1 : slots <= 2 * G ? 2 : 0;
+}
+
+// (a, bf): sub-batch j's view; sums0 / proj0: sub-batch 0's ([sub][m.nch][2 n] / the sample stream's; j == 0:
+// m is not read); part: [j + 1][G][2 n] behind run_l
+template <typename T, int NS, class Clear>
+__device__ __forceinline__ void rpar_scan_energy_ahead(const RParArgs& a, const RParBufs<T>& bf, const double* sums0,
+                                                       const double* proj0, const RParMerge& m, int j, int c,
+                                                       int32_t nchunks, const double* work_in, double* work_out,
+                                                       const double* pre, double* run_l, Clear clear) {
+    const int n = a.n, ld = a.ld, tid = threadIdx.x;
+    const int64_t calls = 2 * (int64_t)a.B;
+    const int64_t c0 = (int64_t)c * kScanChunk, c1 = min<int64_t>(calls, c0 + kScanChunk);
+    __shared__ int act_l[kScanChunk / 2];
+    __shared__ double hand[128];  // [2 n], n <= 64: the running values between two slots
+    const int nsamp = (int)(c1 - c0) / 2;
+    int pent = -1, prel = -1;
+    if (tid < 4 * nsamp) {
+        const int64_t kk = c0 / 2 + (tid >> 2);
+        const int u = (tid >> 1) & 1, role = tid & 1;
+        const int i0 = a.si[kk], jj = a.sj[kk];
+        const int h = a.heads[i0], tt = a.tails[i0];
+        const int hh = u ? (a.side[kk] ? h : jj) : h;
+        const int th = u ? (a.side[kk] ? jj : tt) : tt;
+        pent = role ? th : hh;
+        prel = a.rels[i0];
+    }
+    // the relation rows of the wave's samples
+    const int w = tid >> 6, nw = blockDim.x >> 6, l = lane_id();
+    T vr[kScanWaveSamples][2];
+#pragma unroll
+    for (int q = 0; q < kScanWaveSamples; ++q) {
+        const int64_t kk = c0 / 2 + w + q * nw;
+        vr[q][0] = vr[q][1] = T(0);
+        if (kk < c1 / 2) lane_pair_load(bf.rel + (int64_t)a.rels[a.si[kk]] * ld, n, vr[q]);
+    }
+    const int E2 = 2 * n, G = max(1, (int)blockDim.x / E2);
+    const int g = tid / E2, e = tid - g * E2;
+    const int side = e >= n ? 1 : 0, i = e - side * n;
+    const bool grouped = g < G;
+    const int nslots = kScanQuarters * (j + 1);
+    double* part = run_l + kScanChunk * E2;
+    double w0 = 0.0;  // what the first set starts from
+    if (tid < E2) w0 = (pre && j == 0) ? pre[(int64_t)c * E2 + tid] : work_in[tid];
+    // every set's parts (rpar_scan_parts), ahead of the calls: sixteen values in flight here and sixteen a slot
+    // there are more than the 128 registers of a 1024-thread block hold together (the calls first: they spill)
+    if (grouped)
+        for (int s = 0; s <= j; ++s) {
+            const bool own = s == j;
+            if (own && pre) break;
+            const int cs = own ? c : m.nch - 1;
+            const double* sm = sums0 + (int64_t)s * m.nch * E2;
+            double sq[4] = {0, 0, 0, 0};
+            for (int q0 = g * 16; q0 < cs; q0 += G * 16) {
+                double y[16];
+#pragma unroll
+                for (int q = 0; q < 16; ++q) y[q] = q0 + q < cs ? sm[(int64_t)(q0 + q) * E2 + e] : 0.0;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) sq[q & 3] += y[q];
+            }
+            part[(s * G + g) * E2 + e] = (sq[0] + sq[1]) + (sq[2] + sq[3]);
+        }
+    // the calls of this thread's slots: set s = slot / kScanQuarters -- the last chunk of sub-batch s < j, chunk c
+    // of sub-batch j -- and its run slot % kScanQuarters
+    double x[NS][16];
+    int cnt[NS];  // the calls of the slot
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+        const int slot = g + q * G;
+        cnt[q] = 0;
+        if (grouped && slot < nslots) {
+            const int s = slot / kScanQuarters, qd = slot - s * kScanQuarters;
+            const bool own = s == j;
+            const int64_t k0 = (int64_t)(own ? c : m.nch - 1) * kScanChunk + 16 * qd;
+            const int64_t k1 = min<int64_t>(2 * (int64_t)(own ? a.B : m.Bs), k0 + 16);
+            cnt[q] = (int)max<int64_t>(0, k1 - k0);
+            const double* pj = proj0 + (((int64_t)s * m.Bs * 2 + k0) * 2 + side) * ld + i;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) x[q][k] = k < cnt[q] ? pj[(int64_t)k * 2 * ld] : 0.0;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) x[q][k] = 0.0;
+        }
+    }
+    if (tid < E2) hand[tid] = w0;
+    __syncthreads();
+    for (int t = 0; t < nslots; ++t) {  // the chain: slot t's threads
+        const int s = t / kScanQuarters, qd = t - s * kScanQuarters;
+        const bool own = s == j;
+#pragma unroll
+        for (int q = 0; q < NS; ++q)
+            if (grouped && t == g + q * G) {
+                double run = hand[e];
+                if (qd == 0 && !(own && pre)) {  // rpar_scan_start
+                    double p = 0.0;
+                    for (int gg = 0; gg < G; ++gg) p += part[(s * G + gg) * E2 + e];
+                    run += p;
+                }
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if (k < cnt[q]) {
+                        run += x[q][k];
+                        if (own) run_l[(16 * qd + k) * E2 + e] = run;
+                    }
+                hand[e] = run;
+                if (own && qd == kScanQuarters - 1 && work_out && c == nchunks - 1) work_out[e] = run;
+            }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < kScanWaveSamples; ++q) {
+        const int64_t kk = c0 / 2 + w + q * nw;
+        if (kk >= c1 / 2) continue;
+        const double* pp = run_l + (kk * 2 - c0) * 2 * n;  // [pos: head n, tail n][neg: head n, tail n]
+        double ep = 0, en = 0;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int ii = 2 * l + k;
+            if (ii >= n) continue;
+            const double dp = pp[n + ii] - pp[ii] - (double)vr[q][k];
+            const double dn = pp[3 * n + ii] - pp[2 * n + ii] - (double)vr[q][k];
+            ep += a.l1 ? fabs(dp) : dp * dp;
+            en += a.l1 ? fabs(dn) : dn * dn;
+        }
+        ep = wave_sum(ep);
+        en = wave_sum(en);
+        const bool active = ep + a.margin > en;
+        if (l == 0) {
+            a.act[kk] = active ? 1 : 0;
+            a.loss[kk] = active ? a.margin + ep - en : 0.0;
+            act_l[kk - c0 / 2] = active;
+        }
+    }
+    clear();
+    __syncthreads();
+    if (pent >= 0 && act_l[tid >> 2]) ptab_insert(a, prel, pent, (int)(c0 / 2) * 4 + tid);
+}
+
 template <typename T>
 __global__ __launch_bounds__(1024) void rpar_scan_energy_kernel(RParArgs a, RParBufs<T> bf, const double* sums,
                                                                 int32_t nchunks, const double* work_in,
@@ -1388,6 +1671,19 @@ __global__ __launch_bounds__(1024) void rpar_scan_energy_kernel(RParArgs a, RPar
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double* run_l = (double*)smem;  // [kScanChunk][2 n]
     rpar_scan_energy_block<T>(a, bf, sums, blockIdx.x, nchunks, work_in, work_out, pre, run_l, [&] {
+        ptab_clear_next(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    });
+}
+
+// kPassOptScan (a kernel of its own: the path before keeps its registers and its LDS)
+template <typename T>
+__global__ __launch_bounds__(1024) void rpar_scan_energy_ahead_kernel(RParArgs a, RParBufs<T> bf, const double* sums,
+                                                                      int32_t nchunks, const double* work_in,
+                                                                      double* work_out, const double* pre) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* run_l = (double*)smem;  // [kScanChunk][2 n], then the parts [G][2 n]
+    rpar_scan_energy_ahead<T, 1>(a, bf, sums, a.proj, RParMerge{}, 0, blockIdx.x, nchunks, work_in, work_out, pre,
+                                 run_l, [&] {
         ptab_clear_next(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
     });
 }
@@ -1443,6 +1739,28 @@ __global__ __launch_bounds__(1024) void rpar_scan_energy_merged_kernel(RParArgs 
                               j == m.sub - 1 ? work_out : nullptr, nullptr, run_l, [&] {
         ptab_clear_group(a, m.sub, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
     });
+}
+
+// kPassOptScan: the merged launch (the host takes it when rpar_scan_ahead_slots holds for every sub-batch)
+template <typename T>
+__global__ __launch_bounds__(1024) void rpar_scan_energy_merged_ahead_kernel(RParArgs a, RParBufs<T> bf, RParMerge m,
+                                                                             const double* sums,
+                                                                             const double* work_in,
+                                                                             double* work_out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    double* run_l = (double*)smem;  // [kScanChunk][2 n], then the parts [j + 1][G][2 n]
+    const int j = blockIdx.x / m.nch, c = blockIdx.x - j * m.nch;
+    auto clear = [&] {
+        ptab_clear_group(a, m.sub, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+    };
+    const double* proj0 = a.proj;
+    rpar_sub_view(a, bf, m, j);
+    const int nchunks = (int)((2 * (int64_t)a.B + kScanChunk - 1) / kScanChunk);
+    double* wout = j == m.sub - 1 ? work_out : nullptr;
+    if (rpar_scan_ahead_slots(bf.pass_opt, a.n, j) == 1)
+        rpar_scan_energy_ahead<T, 1>(a, bf, sums, proj0, m, j, c, nchunks, work_in, wout, nullptr, run_l, clear);
+    else
+        rpar_scan_energy_ahead<T, 2>(a, bf, sums, proj0, m, j, c, nchunks, work_in, wout, nullptr, run_l, clear);
 }
 
 // ---- per-epoch tile index --------------------------------------------------
