@@ -6,13 +6,14 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH ?= gfx950
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -fPIC -std=c++17 -ffp-contract=off -Wall -Iinclude
 
-CSRC := $(filter-out kb2e_amd/csrc/eval.hip kb2e_amd/csrc/predict.hip kb2e_amd/csrc/eval_shared.hpp kb2e_amd/csrc/predict_host.hpp kb2e_amd/csrc/joint_host.hpp kb2e_amd/csrc/path_host.hpp kb2e_amd/csrc/classify.hip kb2e_amd/csrc/classify_host.hpp kb2e_amd/csrc/complete.hip kb2e_amd/csrc/complete_host.hpp kb2e_amd/csrc/neighbors.hip kb2e_amd/csrc/neighbors_host.hpp kb2e_amd/csrc/foldin.hip kb2e_amd/csrc/foldin_host.hpp kb2e_amd/csrc/foldrel.hip kb2e_amd/csrc/foldrel_host.hpp kb2e_amd/csrc/textio.hip kb2e_amd/csrc/transr_cons.hip kb2e_amd/csrc/kernels_transr_cons.hpp kb2e_amd/csrc/kernels_transr_wave.hpp kb2e_amd/csrc/kernels_transr_seq.hpp kb2e_amd/csrc/kernels_transr_pipe.hpp kb2e_amd/csrc/kernels_transr_chainw.hpp kb2e_amd/csrc/kernels_transr_chainwp.hpp kb2e_amd/csrc/kernels_transr_chaing.hpp kb2e_amd/csrc/transr_wide.hip kb2e_amd/csrc/kernels_transr_widep.hpp,$(wildcard kb2e_amd/csrc/*.hip kb2e_amd/csrc/*.hpp kb2e_amd/csrc/*.inc)) include/kb2e_engine.h
+CSRC := $(filter-out kb2e_amd/csrc/eval.hip kb2e_amd/csrc/predict.hip kb2e_amd/csrc/eval_shared.hpp kb2e_amd/csrc/predict_host.hpp kb2e_amd/csrc/joint_host.hpp kb2e_amd/csrc/path_host.hpp kb2e_amd/csrc/classify.hip kb2e_amd/csrc/classify_host.hpp kb2e_amd/csrc/complete.hip kb2e_amd/csrc/complete_host.hpp kb2e_amd/csrc/neighbors.hip kb2e_amd/csrc/neighbors_host.hpp kb2e_amd/csrc/candidates.hip kb2e_amd/csrc/candidates_host.hpp kb2e_amd/csrc/foldin.hip kb2e_amd/csrc/foldin_host.hpp kb2e_amd/csrc/foldrel.hip kb2e_amd/csrc/foldrel_host.hpp kb2e_amd/csrc/textio.hip kb2e_amd/csrc/transr_cons.hip kb2e_amd/csrc/kernels_transr_cons.hpp kb2e_amd/csrc/kernels_transr_wave.hpp kb2e_amd/csrc/kernels_transr_seq.hpp kb2e_amd/csrc/kernels_transr_pipe.hpp kb2e_amd/csrc/kernels_transr_chainw.hpp kb2e_amd/csrc/kernels_transr_chainwp.hpp kb2e_amd/csrc/kernels_transr_chaing.hpp kb2e_amd/csrc/transr_wide.hip kb2e_amd/csrc/kernels_transr_widep.hpp,$(wildcard kb2e_amd/csrc/*.hip kb2e_amd/csrc/*.hpp kb2e_amd/csrc/*.inc)) include/kb2e_engine.h
 
 BINS := bin/trainTransE bin/trainTransH bin/trainTransR bin/evalTransE bin/evalTransH bin/evalTransR \
 	bin/predictTransE bin/predictTransH bin/predictTransR bin/classifyTransE bin/classifyTransH bin/classifyTransR \
 	bin/completeTransE bin/completeTransH bin/completeTransR bin/foldinTransE bin/foldinTransH bin/foldinTransR \
 	bin/foldrelTransE bin/foldrelTransH bin/foldrelTransR bin/jointTransE bin/jointTransH bin/jointTransR \
-	bin/pathTransE bin/pathTransH bin/pathTransR bin/neighborsTransE bin/neighborsTransH bin/neighborsTransR
+	bin/pathTransE bin/pathTransH bin/pathTransR bin/neighborsTransE bin/neighborsTransH bin/neighborsTransR \
+	bin/candidatesTransE bin/candidatesTransH bin/candidatesTransR
 
 all: kb2e_amd/libkb2e.so bin/kb2e $(BINS) oracle bin/textio_check
 
@@ -66,6 +67,13 @@ kb2e_amd/build/neighbors.o: kb2e_amd/csrc/neighbors.hip kb2e_amd/csrc/neighbors.
 	@mkdir -p kb2e_amd/build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ kb2e_amd/csrc/neighbors.hip
 
+# candidate lists (kb2e_score_candidates, kb2e_rank_candidates)
+kb2e_amd/build/candidates.o: kb2e_amd/csrc/candidates.hip kb2e_amd/csrc/candidates.hpp kb2e_amd/csrc/candidates_host.hpp \
+		kb2e_amd/csrc/predict.hpp kb2e_amd/csrc/eval.hpp kb2e_amd/csrc/eval_shared.hpp kb2e_amd/csrc/hip_util.hpp \
+		kb2e_amd/csrc/host_data.hpp kb2e_amd/csrc/glibc_rand.hpp kb2e_amd/csrc/kernels_common.hpp
+	@mkdir -p kb2e_amd/build
+	$(HIPCC) $(HIPFLAGS) -c -o $@ kb2e_amd/csrc/candidates.hip
+
 # entity fold-in (kb2e_fold_in_entities)
 kb2e_amd/build/foldin.o: kb2e_amd/csrc/foldin.hip kb2e_amd/csrc/foldin.hpp kb2e_amd/csrc/foldin_host.hpp \
 		kb2e_amd/csrc/classify_host.hpp kb2e_amd/csrc/predict.hpp kb2e_amd/csrc/eval.hpp kb2e_amd/csrc/eval_shared.hpp \
@@ -101,7 +109,7 @@ kb2e_amd/build/transr_wide.o: kb2e_amd/csrc/transr_wide.hip kb2e_amd/csrc/transr
 	@mkdir -p kb2e_amd/build
 	$(HIPCC) $(HIPFLAGS) -c -o $@ kb2e_amd/csrc/transr_wide.hip
 
-kb2e_amd/libkb2e.so: kb2e_amd/build/engine.o kb2e_amd/build/eval.o kb2e_amd/build/predict.o kb2e_amd/build/classify.o kb2e_amd/build/complete.o kb2e_amd/build/neighbors.o kb2e_amd/build/foldin.o kb2e_amd/build/foldrel.o kb2e_amd/build/textio.o kb2e_amd/build/transr_cons.o \
+kb2e_amd/libkb2e.so: kb2e_amd/build/engine.o kb2e_amd/build/eval.o kb2e_amd/build/predict.o kb2e_amd/build/classify.o kb2e_amd/build/complete.o kb2e_amd/build/neighbors.o kb2e_amd/build/candidates.o kb2e_amd/build/foldin.o kb2e_amd/build/foldrel.o kb2e_amd/build/textio.o kb2e_amd/build/transr_cons.o \
 		kb2e_amd/build/transr_wide.o
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
@@ -112,7 +120,7 @@ kb2e_amd/build/engine_prof.o: $(CSRC)
 	@mkdir -p kb2e_amd/build
 	$(HIPCC) $(HIPFLAGS) -DKB2E_OWNER_PROF -c -o $@ kb2e_amd/csrc/engine.hip
 
-kb2e_amd/libkb2e_prof.so: kb2e_amd/build/engine_prof.o kb2e_amd/build/eval.o kb2e_amd/build/predict.o kb2e_amd/build/classify.o kb2e_amd/build/complete.o kb2e_amd/build/neighbors.o kb2e_amd/build/foldin.o kb2e_amd/build/foldrel.o kb2e_amd/build/textio.o \
+kb2e_amd/libkb2e_prof.so: kb2e_amd/build/engine_prof.o kb2e_amd/build/eval.o kb2e_amd/build/predict.o kb2e_amd/build/classify.o kb2e_amd/build/complete.o kb2e_amd/build/neighbors.o kb2e_amd/build/candidates.o kb2e_amd/build/foldin.o kb2e_amd/build/foldrel.o kb2e_amd/build/textio.o \
 		kb2e_amd/build/transr_cons.o kb2e_amd/build/transr_wide.o
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
@@ -168,7 +176,7 @@ $(SANOBJ)/%.o: kb2e_amd/csrc/%.hip $(CSRC)
 	@mkdir -p $(SANOBJ)
 	$(HIPCC) $(HIPFLAGS) $(HIPSAN) -g -c -o $@ $<
 
-kb2e_amd/libkb2e_san.so: $(SANOBJ)/engine.o $(SANOBJ)/eval.o $(SANOBJ)/predict.o $(SANOBJ)/classify.o $(SANOBJ)/complete.o $(SANOBJ)/neighbors.o $(SANOBJ)/foldin.o $(SANOBJ)/foldrel.o $(SANOBJ)/textio.o $(SANOBJ)/transr_cons.o \
+kb2e_amd/libkb2e_san.so: $(SANOBJ)/engine.o $(SANOBJ)/eval.o $(SANOBJ)/predict.o $(SANOBJ)/classify.o $(SANOBJ)/complete.o $(SANOBJ)/neighbors.o $(SANOBJ)/candidates.o $(SANOBJ)/foldin.o $(SANOBJ)/foldrel.o $(SANOBJ)/textio.o $(SANOBJ)/transr_cons.o \
 		$(SANOBJ)/transr_wide.o
 	$(HIPCC) $(HIPFLAGS) $(HIPSAN) -shared-libasan -shared -o $@ $^ -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
 
@@ -177,7 +185,7 @@ bin/san/kb2e: kb2e_amd/csrc/host/kb2e_cli.cpp kb2e_amd/csrc/classify_host.hpp kb
 	$(CLANGXX) -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all -shared-libasan \
 	    -std=c++17 -Iinclude -o $@ kb2e_amd/csrc/host/kb2e_cli.cpp -Lkb2e_amd -l:libkb2e_san.so \
 	    -Wl,-rpath,'$$ORIGIN/../../kb2e_amd' -Wl,-rpath,$$(dirname $$($(CLANGXX) -print-file-name=libclang_rt.asan-x86_64.so))
-	for b in trainTransE trainTransH trainTransR evalTransE evalTransH evalTransR predictTransE predictTransH predictTransR classifyTransE classifyTransH classifyTransR completeTransE completeTransH completeTransR foldinTransE foldinTransH foldinTransR foldrelTransE foldrelTransH foldrelTransR jointTransE jointTransH jointTransR pathTransE pathTransH pathTransR neighborsTransE neighborsTransH neighborsTransR; do ln -sf kb2e bin/san/$$b; done
+	for b in trainTransE trainTransH trainTransR evalTransE evalTransH evalTransR predictTransE predictTransH predictTransR classifyTransE classifyTransH classifyTransR completeTransE completeTransH completeTransR foldinTransE foldinTransH foldinTransR foldrelTransE foldrelTransH foldrelTransR jointTransE jointTransH jointTransR pathTransE pathTransH pathTransR neighborsTransE neighborsTransH neighborsTransR candidatesTransE candidatesTransH candidatesTransR; do ln -sf kb2e bin/san/$$b; done
 
 clean:
 	rm -f kb2e_amd/libkb2e.so kb2e_amd/build/*.o bin/kb2e $(BINS) $(BINDING)

@@ -598,6 +598,71 @@ kb2e_status kb2e_neighbors(kb2e_ctx* ctx, const int32_t* entities, int64_t nq, i
                            int32_t include_self, int32_t* ids /* [nq][k] */, double* dist /* [nq][k] */,
                            int32_t* found /* [nq] */);
 
+/* Candidate lists: score or rank a triple pattern against a list of entities
+ * the caller supplies (fixed negatives of a sampled evaluation, the entities
+ * seen in a slot of a relation, the output of a retriever or of another query)
+ * instead of all |E|.  The contract of the calls above: read-only, stateless
+ * FP64 energies (transr_compat ignored), FP32 tables widened first, every
+ * model, distance, precision and dim, every device buffer freed before return
+ * (also on the error paths), one stream synchronisation, at the end.
+ *   Lists.  List l is candidates[offsets[l] .. offsets[l+1]-1]; offsets[0] == 0,
+ *   offsets does not decrease, an empty list is legal, offsets[nlists] <=
+ *   2^31 - 1.  Query q uses list lists[q]; lists == NULL means list q and needs
+ *   nlists == nq.  Many queries may name one list (one pool per relation and
+ *   slot): it is uploaded once and expanded nowhere, host or device.
+ *   Query.  (entities[q], relations[q], side[q]) as kb2e_predict's: with
+ *   side 1 a listing x stands for the triple (e, x, r), with side 0 for
+ *   (x, e, r).  x == e is a legal listing.
+ *   Energy.  What kb2e_score_triples returns for that triple, bit for bit.
+ *   kb2e_score_candidates.  energy holds the queries' energies back to back in
+ *   query order: query q starts at the sum of the list lengths of the queries
+ *   before it, and its listings keep the list's order; a duplicate listing gets
+ *   its own, equal, entry.
+ *   kb2e_rank_candidates.  ranks[q*2+0] = 1 + the listings x != truth[q] whose
+ *   energy is strictly below that of the truth's triple (ties are not counted
+ *   above the truth; every listing counts, duplicates too); ranks[q*2+1] = the
+ *   same without the listings whose triple is in the filter set (a set:
+ *   duplicates count once; nfilter == 0 with NULL arrays is legal).
+ *   counted[q*2+0..1] = the listings that took part in each comparison --
+ *   x != truth, and for the second also not in the filter -- which a caller
+ *   needs to normalise a rank.  A listing equal to truth[q] is ignored and the
+ *   truth need not be in its list; an empty list gives rank 1, counted 0.  With
+ *   a list that names every entity once the two columns are the matching two
+ *   columns of kb2e_rank_triples.  The ranking is fused: no energy leaves the
+ *   card, and the filter is probed only for listings that count (all listings
+ *   x != truth when counted is asked for, else those below the truth).
+ * TransR never projects per listing: per chunk and relation the distinct
+ * entities (anchors, truths, listings) are projected once into a compact
+ * table, or the whole entity table where they are at least half of |E|
+ * (KB2E_CANDIDATES_PROJECT=compact|full forces either; the result does not
+ * depend on it).  Nothing of size nq x |E| and no expanded triple array is
+ * allocated.  Besides the candidate array, the filter set and the per-query
+ * counters of the ranks, the call's device memory does not depend on nq: the
+ * queries are walked in chunks of at most 2^21 listings and 2^20 queries (a
+ * query is never split; one longer list is a chunk of its own), and a chunk
+ * holds 8 bytes of energy per listing, a 32-byte work item per 64 listings or
+ * shorter list, and for TransR 4 bytes per distinct entity, an |E| x 4-byte
+ * remap and one projected table of dim x min(distinct, |E|) x 8 bytes.  The
+ * cap: 16 MiB of energies, 64 MiB of work items (lists of one listing; 1 MiB
+ * for lists of 64 and more), 16 MiB of distinct entities, the remap and that
+ * one table (KB2E_CANDIDATES_CHUNK=<listings> lowers the chunk, for tests).  The results
+ * do not depend on the launch geometry, the chunking, the projection path or
+ * on whether a list is shared or private.
+ * KB2E_EINVAL: nq < 1, nlists < 1, a malformed offsets, lists[q] outside
+ * 0..nlists-1, lists == NULL with nlists != nq, a side other than 0 / 1, an id
+ * out of range in a query, in truth, in candidates or in the filter, a NULL
+ * array with a count > 0.  KB2E_ESTATE: no embeddings on the device. */
+kb2e_status kb2e_score_candidates(kb2e_ctx* ctx, const int32_t* entities, const int32_t* relations, const int32_t* side,
+                                  const int32_t* lists /* [nq] or NULL */, int64_t nq,
+                                  const int64_t* offsets /* [nlists + 1] */, const int32_t* candidates, int64_t nlists,
+                                  double* energy /* query-major */);
+kb2e_status kb2e_rank_candidates(kb2e_ctx* ctx, const int32_t* entities, const int32_t* relations, const int32_t* side,
+                                 const int32_t* truth /* [nq] */, const int32_t* lists /* [nq] or NULL */, int64_t nq,
+                                 const int64_t* offsets /* [nlists + 1] */, const int32_t* candidates, int64_t nlists,
+                                 const int32_t* filter_heads, const int32_t* filter_tails,
+                                 const int32_t* filter_relations, int64_t nfilter, int64_t* ranks /* [nq][2] */,
+                                 int64_t* counted /* [nq][2] or NULL */);
+
 /* ---- Entity fold-in: give new entities a row without retraining.  The free
  * entities' rows of the device entity table are learnt from example triples
  * while everything else is frozen: every other entity row, the relation and
@@ -789,7 +854,11 @@ int32_t kb2e_rng_next(kb2e_ctx* ctx);
  * sweeps); kb2e_corrupt_triples: "classify_corrupt"; kb2e_complete_triples:
  * "complete_score" (projection + the tile kernel), "complete_select";
  * kb2e_neighbors: "neighbors_score" (projection + the fused score and select
- * kernel), "neighbors_merge"; kb2e_fold_in_entities: "foldin"; kb2e_fold_in_relations: "foldrel").  Returns total
+ * kernel), "neighbors_merge"; kb2e_score_candidates / kb2e_rank_candidates:
+ * "candidates_project" (TransR: the compact or full projection of a chunk's
+ * relation), "candidates_score", "candidates_rank" (the work-item kernel, with
+ * the comparisons, filter probes and counts when ranking);
+ * kb2e_fold_in_entities: "foldin"; kb2e_fold_in_relations: "foldrel").  Returns total
  * milliseconds and launch count since kb2e_profile_enable.  on = 0: off;
  * on = P >= 1: the batch kernels of every P-th batch are timed (event records
  * cost device time of their own; sampling keeps the rest of the run unperturbed),
@@ -811,6 +880,12 @@ kb2e_status kb2e_profile_query(kb2e_ctx* ctx, const char* name, double* total_ms
  * "neighbors_chunks" -- runs of queries that shared the partial records,
  * "neighbors_prunes" -- cuts of a row's list to its k best, each of which
  * lowered that row's bound.
+ * Of the last kb2e_score_candidates / kb2e_rank_candidates call:
+ * "candidates_listings" -- listings scored, "candidates_items" -- wave-sized
+ * work items (at most 64 listings each; 63 when ranking, where the last lane
+ * scores the truth), "candidates_chunks" -- runs of queries that shared the
+ * device buffers, "candidates_projections" -- TransR projections made (one per
+ * chunk and relation), "candidates_probes" -- filter-set probes.
  * Of the last kb2e_predict_joint / kb2e_rank_joint call (kept on the host):
  * "joint_chunks" -- runs of queries that shared the key buffer, "joint_rows" --
  * constraint rows scored, "joint_projections" -- per-relation projections made.

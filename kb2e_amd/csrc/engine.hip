@@ -32,6 +32,7 @@
 #include "classify.hpp"
 #include "complete.hpp"
 #include "neighbors.hpp"
+#include "candidates.hpp"
 #include "foldin.hpp"
 #include "foldrel.hpp"
 #include "host_data.hpp"
@@ -182,6 +183,7 @@ struct kb2e_ctx {
     DevBuf hpar_clk;                       // KB2E_HPAR_CLK: the w-apply workgroups' clocks (diagnostic)
     CompleteStats complete_stats;  // kb2e_complete_triples: the last call's counters (kb2e_counter)
     NeighborsStats neighbors_stats;  // kb2e_neighbors: likewise
+    CandidatesStats candidates_stats;  // kb2e_score_candidates / kb2e_rank_candidates: likewise
     JointStats joint_stats;        // kb2e_predict_joint / kb2e_rank_joint: likewise
     PathStats path_stats;          // kb2e_predict_path / kb2e_rank_path: likewise
     DevBuf hpar_count;                     // PARALLEL TransH: normOrth iterations of the last two batches, relation passes run
@@ -2152,6 +2154,44 @@ kb2e_status kb2e_neighbors(kb2e_ctx* c, const int32_t* entities, int64_t nq, int
     });
 }
 
+kb2e_status kb2e_score_candidates(kb2e_ctx* c, const int32_t* entities, const int32_t* relations, const int32_t* side,
+                                  const int32_t* lists, int64_t nq, const int64_t* offsets, const int32_t* candidates,
+                                  int64_t nlists, double* energy) {
+    return guarded(c, [&] {
+        if (!entities || !relations || !side || nq < 1 || !offsets || nlists < 1 || !energy)
+            return fail(c, KB2E_EINVAL, "no queries or no lists, or a NULL array with a count > 0");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        c->candidates_stats = CandidatesStats{};
+        score_candidates(eval_tables(c),
+                         CandidatesQuery{entities, relations, side, nullptr, lists, nq, offsets, candidates, nlists,
+                                         nullptr, nullptr, nullptr, 0},
+                         energy, &c->candidates_stats, &hooks);
+        return KB2E_OK;
+    });
+}
+
+kb2e_status kb2e_rank_candidates(kb2e_ctx* c, const int32_t* entities, const int32_t* relations, const int32_t* side,
+                                 const int32_t* truth, const int32_t* lists, int64_t nq, const int64_t* offsets,
+                                 const int32_t* candidates, int64_t nlists, const int32_t* fh, const int32_t* ft,
+                                 const int32_t* fr, int64_t nfilter, int64_t* ranks, int64_t* counted) {
+    return guarded(c, [&] {
+        if (!entities || !relations || !side || !truth || nq < 1 || !offsets || nlists < 1 || !ranks || nfilter < 0 ||
+            (nfilter > 0 && (!fh || !ft || !fr)))
+            return fail(c, KB2E_EINVAL, "no queries or no lists, or a NULL array with a count > 0");
+        if (!c->have_params) return fail(c, KB2E_ESTATE, "no embeddings on the device");
+        HIPCHK(hipSetDevice(c->cfg.device));
+        const PredictHooks hooks = predict_hooks(c);
+        c->candidates_stats = CandidatesStats{};
+        rank_candidates(eval_tables(c),
+                        CandidatesQuery{entities, relations, side, truth, lists, nq, offsets, candidates, nlists, fh, ft,
+                                        fr, nfilter},
+                        ranks, counted, &c->candidates_stats, &hooks);
+        return KB2E_OK;
+    });
+}
+
 kb2e_status kb2e_fold_in_entities(kb2e_ctx* c, const int32_t* free_entities, int64_t nfree, const int32_t* heads,
                                   const int32_t* tails, const int32_t* relations, int64_t count, const int32_t* kh,
                                   const int32_t* kt, const int32_t* kr, int64_t nknown, int32_t epochs, uint64_t seed,
@@ -2240,6 +2280,14 @@ kb2e_status kb2e_counter(kb2e_ctx* c, const char* name, int64_t* value) {
             if (nm == "neighbors_slices") return *value = ns.slices, KB2E_OK;
             if (nm == "neighbors_chunks") return *value = ns.chunks, KB2E_OK;
             if (nm == "neighbors_prunes") return *value = ns.prunes, KB2E_OK;
+        }
+        if (value && nm.rfind("candidates_", 0) == 0) {  // kb2e_score_candidates / kb2e_rank_candidates: the last call
+            const CandidatesStats& cs = c->candidates_stats;
+            if (nm == "candidates_listings") return *value = cs.listings, KB2E_OK;
+            if (nm == "candidates_items") return *value = cs.items, KB2E_OK;
+            if (nm == "candidates_chunks") return *value = cs.chunks, KB2E_OK;
+            if (nm == "candidates_projections") return *value = cs.projections, KB2E_OK;
+            if (nm == "candidates_probes") return *value = cs.probes, KB2E_OK;
         }
         if (value && nm.rfind("joint_", 0) == 0) {  // kb2e_predict_joint / kb2e_rank_joint: the last call
             const JointStats& js = c->joint_stats;

@@ -14,7 +14,10 @@
 // several patterns at once) and pathTransE / pathTransH / pathTransR (path
 // queries: the top-k entities at the end of a relation path) and
 // neighborsTransE / neighborsTransH / neighborsTransR (entity neighbours: the
-// k nearest entities of given entities or of all, and the mutual pairs).
+// k nearest entities of given entities or of all, and the mutual pairs) and
+// candidatesTransE / candidatesTransH / candidatesTransR (candidate lists:
+// given entities ordered and a truth ranked among them; type-constrained
+// evaluation).
 //
 // Same flags, defaults, stdout lines and files as the reference binaries
 // (transe/bin/trainTransE.cpp, common/args.cpp, common/loader.cpp,
@@ -144,6 +147,7 @@ void printUsage(const char* invoked) {  // common/args.cpp:125-142
     printf("   --topk [10] --constrained [1] (completeTrans*: heads / tails from the entities seen in that slot of the relation)\n");
     printf("   --loops [0] (completeTrans*: 1 = head == tail may be an answer)\n");
     printf("   --filtered [1] (completeTrans*: known = train + valid + test; 0 = train + valid)\n");
+    printf("   --queries FILE | --typed (candidatesTrans*: head<TAB>tail<TAB>relation<TAB>cand,cand,...[<TAB>truth] lines with ? in the unknown slot; or the type-constrained metrics of test.txt)\n");
     printf("   --entities FILE | --all, --topk [10] --relation NAME --self --pairs (neighborsTrans*: entity names, one per line, or every entity; the space of a relation instead of the entity space; the entity itself is a candidate; the mutual pairs instead of the lists)\n");
     printf("   --new FILE --foldout DIR (foldinTrans*: triples that mention the new entities; where the full entity table goes)\n");
     printf("   --epochs [1000] --seed [now] --side [2] (foldinTrans*: passes, seed of the new rows and of the negatives, slot to corrupt)\n");
@@ -1126,6 +1130,188 @@ int neighbors_main(int argc, char** argv, kb2e_model model) {
     return 0;
 }
 
+// candidatesTransE|H|R: candidate lists (kb2e_score_candidates,
+// kb2e_rank_candidates) on the tables evalTrans* loads.  --queries FILE: lines
+// "head<TAB>tail<TAB>relation<TAB>cand,cand,...[<TAB>truth]" with a literal ? in
+// the unknown head or tail; unknown names are reported in the loader's wording
+// (a listing is skipped, a line with an unknown head, tail, relation or truth is
+// dropped).  Per line its listings in ascending (energy, entity id, position in
+// the list) order, one line each: line (from 0), position (from 1), entity
+// name, energy; where a truth is given also "line<TAB>rank<TAB>raw<TAB>filtered
+// <TAB>counted raw<TAB>counted filtered", the filter being train + valid + test
+// as in predictTrans*.  --typed takes no query file: every test triple is ranked
+// on both sides against the entities seen in that slot of its relation in train
+// + valid + test (one shared list per relation and slot), and the metrics are
+// printed beside those against all entities (kb2e_rank_triples).
+void print_rank_metrics(const char* label, const std::vector<int64_t>& ranks, size_t stride, size_t c0, size_t c1) {
+    double sum = 0, rr = 0, h1 = 0, h3 = 0, h10 = 0, count = 0;
+    for (size_t x = 0; x * stride < ranks.size(); ++x)
+        for (size_t c : {c0, c1}) {
+            const double r = (double)ranks[x * stride + c];
+            sum += r;
+            rr += 1.0 / r;
+            h1 += r <= 1;
+            h3 += r <= 3;
+            h10 += r <= 10;
+            count += 1;
+        }
+    printf("%s -- Rank: %f, MRR: %f, Hits@1: %f, Hits@3: %f, Hits@10: %f\n", label, sum / count, rr / count, h1 / count,
+           h3 / count, h10 / count);
+}
+
+int candidates_main(int argc, char** argv, kb2e_model model) {
+    EmbeddingArguments args = parseArgs(argc, argv);
+    printf("%s\n", args.to_string().c_str());
+    int i;
+    std::string queries;
+    if ((i = argpos("queries", true, argc, argv)) != -1) queries = argv[i + 1];
+    const bool typed = argpos("typed", false, argc, argv) != -1;
+    if (typed == !queries.empty()) {
+        printf("Give either --queries FILE or --typed\n");
+        exit(1);
+    }
+    std::ifstream in;
+    if (!typed) {
+        in.open(queries);
+        if (!in) {
+            printf("Could not open query file: %s\n", queries.c_str());
+            exit(2);
+        }
+    }
+    LoadedModel L;
+    load_model(args, model, L);
+    const int64_t nf = (int64_t)L.fh.size();
+    if (typed) {
+        const size_t nt = L.th.size();
+        const int64_t nr = (int64_t)L.relation2id.size();
+        if (nt == 0) {
+            printf("No test triples\n");
+            exit(1);
+        }
+        const kb2e::SlotPools sp = kb2e::build_slot_pools(L.fh.data(), L.ft.data(), L.fr.data(), nf, nr);
+        // per test triple: the head query (side 0, the heads' pool), then the tail query
+        std::vector<int32_t> qe(nt * 2), qr(nt * 2), qs(nt * 2), qt(nt * 2), ql(nt * 2);
+        for (size_t k = 0; k < nt; ++k) {
+            qe[k * 2] = L.tt[k], qt[k * 2] = L.th[k], qs[k * 2] = 0, ql[k * 2] = L.tr[k] * 2;
+            qe[k * 2 + 1] = L.th[k], qt[k * 2 + 1] = L.tt[k], qs[k * 2 + 1] = 1, ql[k * 2 + 1] = L.tr[k] * 2 + 1;
+            qr[k * 2] = qr[k * 2 + 1] = L.tr[k];
+        }
+        std::vector<int64_t> ranks(nt * 4), counted(nt * 4), full(nt * 4);
+        check(L.ctx, kb2e_rank_candidates(L.ctx, qe.data(), qr.data(), qs.data(), qt.data(), ql.data(), (int64_t)nt * 2,
+                                          sp.off.data(), sp.ids.data(), nr * 2, L.fh.data(), L.ft.data(), L.fr.data(), nf,
+                                          ranks.data(), counted.data()), "rank_candidates");
+        check(L.ctx, kb2e_rank_triples(L.ctx, L.th.data(), L.tt.data(), L.tr.data(), (int64_t)nt, L.fh.data(), L.ft.data(),
+                                       L.fr.data(), nf, full.data()), "rank_triples");
+        long long c0 = 0, c1 = 0;
+        for (size_t x = 0; x < nt * 2; ++x) c0 += counted[x * 2], c1 += counted[x * 2 + 1];
+        print_rank_metrics("Typed raw     ", ranks, 4, 0, 2);
+        print_rank_metrics("Typed filtered", ranks, 4, 1, 3);
+        printf("Typed counted  -- raw: %lld, filtered: %lld\n", c0, c1);
+        print_rank_metrics("Full raw      ", full, 4, 0, 2);
+        print_rank_metrics("Full filtered ", full, 4, 1, 3);
+        kb2e_destroy(L.ctx);
+        return 0;
+    }
+    std::vector<std::string> names(L.entity2id.size());
+    for (const auto& kv : L.entity2id)
+        if (kv.second >= 0 && (size_t)kv.second < names.size()) names[(size_t)kv.second] = kv.first;
+    std::vector<int32_t> qe, qr, qs, qt, qline, cand;
+    std::vector<int64_t> off(1, 0);
+    std::string text;
+    for (int line = 0; std::getline(in, text); ++line) {
+        std::vector<std::string> col;
+        size_t b = 0;
+        for (size_t e; (e = text.find('\t', b)) != std::string::npos; b = e + 1) col.push_back(text.substr(b, e - b));
+        col.push_back(text.substr(b));
+        if (!col.empty() && !col.back().empty() && col.back().back() == '\r') col.back().pop_back();
+        if (col.size() == 1 && col[0].empty()) continue;
+        if (col.size() < 4 || col.size() > 5) {
+            std::cout << "Query needs head, tail, relation and candidates: " << text << std::endl;
+            continue;
+        }
+        const bool noHead = col[0] == "?", noTail = col[1] == "?";
+        bool fail = false;
+        if (noHead == noTail) {
+            std::cout << "Query needs exactly one ? in the head or the tail column: " << col[0] << ' ' << col[1] << std::endl;
+            fail = true;
+        }
+        if (!noHead && !L.entity2id.count(col[0])) {
+            std::cout << "Head entity found in triple file that was not found in the identity file: " << col[0] << std::endl;
+            fail = true;
+        }
+        if (!noTail && !L.entity2id.count(col[1])) {
+            std::cout << "Tail entity found in triple file that was not found in the identity file: " << col[1] << std::endl;
+            fail = true;
+        }
+        if (!L.relation2id.count(col[2])) {
+            std::cout << "Relation found in triple file that was not found in the identity file: " << col[2] << std::endl;
+            fail = true;
+        }
+        if (col.size() == 5 && !L.entity2id.count(col[4])) {
+            std::cout << "Entity found in triple file that was not found in the identity file: " << col[4] << std::endl;
+            fail = true;
+        }
+        if (fail) continue;
+        std::stringstream ss(col[3]);
+        for (std::string name; std::getline(ss, name, ',');) {
+            if (name.empty()) continue;
+            if (!L.entity2id.count(name)) {
+                std::cout << "Entity found in triple file that was not found in the identity file: " << name << std::endl;
+                continue;
+            }
+            cand.push_back(L.entity2id[name]);
+        }
+        off.push_back((int64_t)cand.size());
+        qe.push_back(L.entity2id[noTail ? col[0] : col[1]]);
+        qr.push_back(L.relation2id[col[2]]);
+        qs.push_back(noTail ? 1 : 0);
+        qt.push_back(col.size() == 5 ? L.entity2id[col[4]] : -1);
+        qline.push_back(line);
+    }
+    const size_t nq = qe.size();
+    if (nq == 0) {
+        printf("No queries\n");
+        exit(1);
+    }
+    std::vector<double> energy((size_t)std::max<int64_t>(off[nq], 1));
+    check(L.ctx, kb2e_score_candidates(L.ctx, qe.data(), qr.data(), qs.data(), nullptr, (int64_t)nq, off.data(),
+                                       cand.data(), (int64_t)nq, energy.data()), "score_candidates");
+    // the lines with a truth, ranked in one call against their own lists
+    std::vector<int32_t> re, rr, rs, rt, rl;
+    std::vector<int64_t> slot(nq, -1);
+    for (size_t q = 0; q < nq; ++q)
+        if (qt[q] >= 0) {
+            slot[q] = (int64_t)re.size();
+            re.push_back(qe[q]), rr.push_back(qr[q]), rs.push_back(qs[q]), rt.push_back(qt[q]), rl.push_back((int32_t)q);
+        }
+    std::vector<int64_t> ranks(re.size() * 2), counted(re.size() * 2);
+    if (!re.empty())
+        check(L.ctx, kb2e_rank_candidates(L.ctx, re.data(), rr.data(), rs.data(), rt.data(), rl.data(), (int64_t)re.size(),
+                                          off.data(), cand.data(), (int64_t)nq, nf ? L.fh.data() : nullptr,
+                                          nf ? L.ft.data() : nullptr, nf ? L.fr.data() : nullptr, nf, ranks.data(),
+                                          counted.data()), "rank_candidates");
+    std::vector<int64_t> order;
+    for (size_t q = 0; q < nq; ++q) {
+        order.resize((size_t)(off[q + 1] - off[q]));
+        for (size_t j = 0; j < order.size(); ++j) order[j] = off[q] + (int64_t)j;
+        std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+            if (energy[(size_t)a] != energy[(size_t)b]) return energy[(size_t)a] < energy[(size_t)b];
+            if (cand[(size_t)a] != cand[(size_t)b]) return cand[(size_t)a] < cand[(size_t)b];
+            return a < b;
+        });
+        for (size_t j = 0; j < order.size(); ++j)
+            printf("%d\t%d\t%s\t%.6lf\n", qline[q], (int)j + 1, names[(size_t)cand[(size_t)order[j]]].c_str(),
+                   energy[(size_t)order[j]]);
+        if (slot[q] >= 0) {
+            const size_t s = (size_t)slot[q];
+            printf("%d\trank\t%lld\t%lld\t%lld\t%lld\n", qline[q], (long long)ranks[s * 2], (long long)ranks[s * 2 + 1],
+                   (long long)counted[s * 2], (long long)counted[s * 2 + 1]);
+        }
+    }
+    kb2e_destroy(L.ctx);
+    return 0;
+}
+
 // foldinTransE|H|R: rows for entities the model was not trained on
 // (kb2e_fold_in_entities).  --datadir D holds entity2id.txt with the old
 // entities first and the new ones after them; the tables in --outdir O have rows
@@ -1446,9 +1632,12 @@ int main(int argc, char** argv) {
     if (prog == "neighborsTransE") return neighbors_main(argc, argv, KB2E_TRANSE);
     if (prog == "neighborsTransH") return neighbors_main(argc, argv, KB2E_TRANSH);
     if (prog == "neighborsTransR") return neighbors_main(argc, argv, KB2E_TRANSR);
+    if (prog == "candidatesTransE") return candidates_main(argc, argv, KB2E_TRANSE);
+    if (prog == "candidatesTransH") return candidates_main(argc, argv, KB2E_TRANSH);
+    if (prog == "candidatesTransR") return candidates_main(argc, argv, KB2E_TRANSR);
     fprintf(stderr,
             "invoke as trainTransE|H|R, evalTransE|H|R, predictTransE|H|R, classifyTransE|H|R, completeTransE|H|R, "
-            "foldinTransE|H|R, foldrelTransE|H|R, jointTransE|H|R, pathTransE|H|R or neighborsTransE|H|R (got %s)\n",
+            "foldinTransE|H|R, foldrelTransE|H|R, jointTransE|H|R, pathTransE|H|R, neighborsTransE|H|R or candidatesTransE|H|R (got %s)\n",
             prog.c_str());
     return 2;
 }

@@ -32,7 +32,7 @@ EXPORTS = [
     "kb2e_rank_triples", "kb2e_predict_relations", "kb2e_rank_relations", "kb2e_fit_thresholds",
     "kb2e_classify_triples", "kb2e_corrupt_triples", "kb2e_complete_triples", "kb2e_fold_in_entities",
     "kb2e_fold_in_relations", "kb2e_predict_joint", "kb2e_rank_joint", "kb2e_predict_path", "kb2e_rank_path",
-    "kb2e_neighbors",
+    "kb2e_neighbors", "kb2e_score_candidates", "kb2e_rank_candidates",
 ]
 COMM_ID_BYTES = 128
 PATH_MAX_HOPS = 8  # KB2E_PATH_MAX_HOPS
@@ -114,6 +114,9 @@ def lib():
             "kb2e_complete_triples": (i32, [vp, i32p, i64, i32, i32p, i32p, i32p, i64, i32, i32, i32p, i32p, dp,
                                             C.POINTER(i64)]),
             "kb2e_neighbors": (i32, [vp, i32p, i64, i32, i32, i32, i32p, dp, i32p]),
+            "kb2e_score_candidates": (i32, [vp, i32p, i32p, i32p, i32p, i64, C.POINTER(i64), i32p, i64, dp]),
+            "kb2e_rank_candidates": (i32, [vp, i32p, i32p, i32p, i32p, i32p, i64, C.POINTER(i64), i32p, i64, i32p, i32p,
+                                           i32p, i64, C.POINTER(i64), C.POINTER(i64)]),
             "kb2e_fold_in_entities": (i32, [vp, i32p, i64, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, i32, C.c_uint64,
                                             i32, i32, dp, dp, dp, C.POINTER(i64)]),
             "kb2e_fold_in_relations": (i32, [vp, i32p, i64, i32p, i32p, i32p, i64, i32p, i32p, i32p, i64, i32, i64,
@@ -672,6 +675,89 @@ class Engine:
     def knn_graph(self, k, relation=-1):
         """neighbors() of every entity, itself left out: row a lists a's k nearest."""
         return self.neighbors(np.arange(self.ne, dtype=np.int32), k, relation=relation)
+
+    # ------------------------------------------------ candidate lists
+    @staticmethod
+    def _candidate_lists(candidates):
+        """A sequence of id arrays as (offsets int64[nlists + 1], flat int32)."""
+        arrs = [np.ascontiguousarray(c, dtype=np.int32).reshape(-1) for c in candidates]
+        off = np.zeros(len(arrs) + 1, np.int64)
+        if arrs:
+            off[1:] = np.cumsum([len(a) for a in arrs])
+        flat = np.concatenate(arrs) if arrs else np.zeros(0, np.int32)
+        return off, np.ascontiguousarray(flat, dtype=np.int32)
+
+    def _candidate_query(self, entities, relations, side, lists):
+        e = np.ascontiguousarray(entities, dtype=np.int32).reshape(-1)
+        r = np.ascontiguousarray(relations, dtype=np.int32).reshape(-1)
+        s = np.ascontiguousarray(side, dtype=np.int32).reshape(-1)
+        if not (len(e) == len(r) == len(s)):
+            raise ValueError("entities, relations and side differ in length")
+        li = None
+        if lists is not None:
+            li = np.ascontiguousarray(lists, dtype=np.int32).reshape(-1)
+            if len(li) != len(e):
+                raise ValueError("lists and entities differ in length")
+        return e, r, s, li
+
+    def score_candidates(self, entities, relations, side, candidates, lists=None):
+        """Energies of one-sided queries against given candidate lists: query q is
+        (entities[q], relations[q], side[q]) as predict()'s and is scored against
+        the list candidates[lists[q]] (lists None: candidates[q]); a listing x is
+        the triple (e, x, r) for side 1 and (x, e, r) for side 0, in score()'s
+        bits.  A list that many queries name is uploaded once.  Returns one
+        float64 array per query, in its list's order."""
+        e, r, s, li = self._candidate_query(entities, relations, side, lists)
+        off, flat = self._candidate_lists(candidates)
+        nq, nl = len(e), len(off) - 1
+        lens = np.diff(off)
+        which = np.arange(nq) if li is None else li
+        ok = nl > 0 and nq > 0 and (li is not None or nl == nq) and which.min(initial=0) >= 0 and which.max(initial=0) < nl
+        total = int(lens[which].sum()) if ok else 0
+        out = np.zeros(max(total, 1))
+        self._check(lib().kb2e_score_candidates(self.h, _ip(e), _ip(r), _ip(s), None if li is None else _ip(li), nq,
+                                                off.ctypes.data_as(C.POINTER(C.c_int64)), _ip(flat), nl, _dp(out)),
+                    "score_candidates")
+        cuts = np.cumsum(lens[which])[:-1]
+        return np.split(out[:total], cuts)
+
+    def rank_candidates(self, entities, relations, side, truth, candidates, filt=None, lists=None):
+        """Rank truth[q] among the listings of query q's list (see
+        score_candidates): ranks int64[nq, 2] = 1 + the listings other than the
+        truth of strictly smaller energy, raw and with the listings whose triple is
+        a row of `filt` left out; counted int64[nq, 2] = the listings that took
+        part in each.  Returns (ranks, counted)."""
+        e, r, s, li = self._candidate_query(entities, relations, side, lists)
+        t = np.ascontiguousarray(truth, dtype=np.int32).reshape(-1)
+        if len(t) != len(e):
+            raise ValueError("truth and entities differ in length")
+        off, flat = self._candidate_lists(candidates)
+        nq, nl = len(e), len(off) - 1
+        fc, nf = self._filter_cols(filt)
+        ranks = np.zeros((max(nq, 1), 2), np.int64)
+        counted = np.zeros((max(nq, 1), 2), np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self._check(lib().kb2e_rank_candidates(self.h, _ip(e), _ip(r), _ip(s), _ip(t), None if li is None else _ip(li), nq,
+                                               off.ctypes.data_as(i64p), _ip(flat), nl,
+                                               *[None if c is None else _ip(c) for c in fc], nf,
+                                               ranks.ctypes.data_as(i64p), counted.ctypes.data_as(i64p)),
+                    "rank_candidates")
+        return ranks[:nq], counted[:nq]
+
+    def rerank(self, entities, relations, side, candidates, k, lists=None):
+        """score_candidates() sorted on the host: per query the k listings of
+        smallest (energy, entity id, position in the list).  Returns per query
+        (ids int32[m], energy float64[m], position int64[m]), m = min(k, listings)."""
+        e, r, s, li = self._candidate_query(entities, relations, side, lists)
+        arrs = [np.ascontiguousarray(c, dtype=np.int32).reshape(-1) for c in candidates]
+        en = self.score_candidates(e, r, s, arrs, lists=li)
+        out = []
+        for q, eq in enumerate(en):
+            ids = arrs[q if li is None else li[q]]
+            pos = np.arange(len(ids), dtype=np.int64)
+            order = np.lexsort((pos, ids, eq))[:max(int(k), 0)]
+            out.append((ids[order], eq[order], pos[order]))
+        return out
 
     # ------------------------------------------------ entity fold-in
     def fold_in(self, free, examples, known=None, *, epochs, seed=0, side=2, max_sweeps=0, rows=None):

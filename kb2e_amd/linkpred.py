@@ -678,3 +678,103 @@ def duplicate_detection(ds, model, dim, count, *, epochs, k=10, seed=0, relation
     out = duplicate_metrics(ids, dist, found, pairs, k)
     out["pairs"] = pairs
     return out
+
+
+# ------------------------------------------------------------ candidate lists
+
+def candidate_metrics(ranks):
+    """``rank_metrics`` plus "hits@3" of a column (or block) of ranks."""
+    ranks = np.asarray(ranks, dtype=np.float64).reshape(-1)
+    out = rank_metrics(ranks)
+    out["hits@3"] = float((ranks <= 3).mean())
+    return out
+
+
+def side_queries(test):
+    """Both one-sided queries of every test triple, interleaved: row 2i asks for
+    the head of triple i (its tail, side 0, truth = the head), row 2i + 1 for the
+    tail (its head, side 1, truth = the tail).  Returns int32 arrays (entities,
+    relations, side, truth) of length 2 * ntest; ranks of these queries reshaped
+    to [ntest, 4] are in ``Engine.rank_triples``' column order."""
+    test = np.asarray(test, dtype=np.int32).reshape(-1, 3)
+    nt = len(test)
+    ent = np.empty(2 * nt, np.int32)
+    truth = np.empty(2 * nt, np.int32)
+    ent[0::2], ent[1::2] = test[:, 1], test[:, 0]
+    truth[0::2], truth[1::2] = test[:, 0], test[:, 1]
+    rel = np.repeat(test[:, 2], 2).astype(np.int32)
+    side = np.tile(np.array([0, 1], np.int32), nt)
+    return ent, rel, side, truth
+
+
+def _candidate_report(ranks, counted):
+    ranks = np.asarray(ranks, dtype=np.int64).reshape(-1, 2)
+    counted = np.asarray(counted, dtype=np.int64).reshape(-1, 2)
+    return {"raw": candidate_metrics(ranks[:, 0]), "filtered": candidate_metrics(ranks[:, 1]),
+            "counted": {"raw": int(counted[:, 0].sum()), "filtered": int(counted[:, 1].sum())},
+            "queries": int(len(ranks)), "ranks": ranks.reshape(-1, 4), "counted_per_query": counted}
+
+
+def sampled_evaluation(eng, test, filt, negatives=500, seed=0):
+    """Link prediction against sampled negatives (the fixed-negatives protocol
+    of large benchmarks): every test triple is ranked on both sides
+    (``side_queries``) among `negatives` entity ids per query, drawn uniformly
+    with ``numpy.random.default_rng(seed)`` -- or among the ids given: an int
+    array [2 * ntest, m] holds one list per query, a 1-d array one list that every
+    query shares.  ``Engine.rank_candidates`` with filter `filt`.  Returns
+    {"raw", "filtered"} -> mean rank, MRR, Hits@1/3/10 over both sides,
+    "counted" -> the listings compared in all (raw, filtered), "queries",
+    "ranks" int64[ntest, 4] (head raw, head filtered, tail raw, tail filtered)
+    and "counted_per_query" int64[2 * ntest, 2]."""
+    ent, rel, side, truth = side_queries(test)
+    nq = len(ent)
+    if nq == 0:
+        raise ValueError("no test triples")
+    if np.ndim(negatives) == 0:
+        m = int(negatives)
+        if m < 0:
+            raise ValueError("negatives must not be negative")
+        lists_of = np.random.default_rng(seed).integers(0, eng.ne, size=(nq, m), dtype=np.int32)
+    else:
+        lists_of = np.asarray(negatives, dtype=np.int32)
+    if lists_of.ndim == 1:
+        ranks, counted = eng.rank_candidates(ent, rel, side, truth, [lists_of], filt, lists=np.zeros(nq, np.int32))
+    elif lists_of.ndim == 2 and len(lists_of) == nq:
+        ranks, counted = eng.rank_candidates(ent, rel, side, truth, list(lists_of), filt)
+    else:
+        raise ValueError("negatives must be a count, one list, or one list per query (2 * ntest of them)")
+    return _candidate_report(ranks, counted)
+
+
+def slot_pools(triples, num_relations):
+    """Per (relation, slot) the distinct entities seen there among `triples`,
+    ascending: a list of 2 * num_relations int32 arrays, relation * 2 + slot
+    (slot 0 = head, 1 = tail) -- classify_host.hpp's build_slot_pools."""
+    t = np.asarray(triples, dtype=np.int64).reshape(-1, 3)
+    pools = []
+    for r in range(int(num_relations)):
+        rows = t[t[:, 2] == r]
+        pools.append(np.unique(rows[:, 0]).astype(np.int32))
+        pools.append(np.unique(rows[:, 1]).astype(np.int32))
+    return pools
+
+
+def type_constrained_evaluation(eng, ds):
+    """Type-constrained link prediction (Krompass et al. 2015): every test triple
+    is ranked on both sides only against the entities observed in that slot of its
+    relation in train + valid + test (``slot_pools``; one shared list per
+    relation and slot, named by many queries), filter = train + valid + test.
+    Returns {"constrained": ``sampled_evaluation``'s report, "unconstrained":
+    {"raw", "filtered", "ranks"} from ``Engine.rank_triples`` on the same
+    triples}."""
+    known = np.concatenate([ds.train, ds.valid, ds.test]).astype(np.int32)
+    test = np.asarray(ds.test, dtype=np.int32).reshape(-1, 3)
+    ent, rel, side, truth = side_queries(test)
+    if len(ent) == 0:
+        raise ValueError("no test triples")
+    pools = slot_pools(known, ds.num_relations)
+    ranks, counted = eng.rank_candidates(ent, rel, side, truth, pools, known, lists=rel * 2 + side)
+    full = np.asarray(eng.rank_triples(test, known), dtype=np.int64).reshape(-1, 4)
+    return {"constrained": _candidate_report(ranks, counted),
+            "unconstrained": {"raw": candidate_metrics(full[:, [0, 2]]), "filtered": candidate_metrics(full[:, [1, 3]]),
+                              "ranks": full}}
